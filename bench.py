@@ -63,7 +63,11 @@ def parse():
     ap.add_argument('--no-cpu', action='store_true', help='skip the cpu_baseline leg')
     ap.add_argument('--no-c3', action='store_true', help='skip the configs[2] variant of the default line')
     ap.add_argument('--no-graph', dest='graph', action='store_false', help='launch every step eagerly instead of replaying a captured HIP graph')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed (the CSR matrix K: a seeded sample of its entries) as DIR/<name>.npy')
     a = ap.parse_args()
+    if a.steps is not None and a.steps < 1 or a.warmup is not None and a.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     c3 = a.config == 'c3'
     a.n = a.n or (64 if c3 else 128)
     a.steps = a.steps if a.steps is not None else (30 if c3 else 200)
@@ -350,6 +354,30 @@ def settle_and_time(wl, steps, warmup, settle, world, dist, use_graph):
     return elapsed, kernel_ms, launch, settle + settle_extra
 
 
+DUMP_ENTRIES = 1 << 20  # entries of K written by --dump-outputs over all ranks: 3 float64 arrays of 8 MB
+
+
+def dump_outputs(wl, out_dir, rank, world):
+    '''--dump-outputs: the matrix a caller of the timed step receives -- K as (values, rowptr, colidx) on this rank -- as float64 .npy files:
+    `values`, `rows` and `cols` of a sample of its entries (positions drawn with default_rng(0) from the pattern: the same on every build
+    that computes the same pattern; all entries when there are fewer) and `summary` = [rows, entries, sum |v|, max |v|, ||v||_2] over all
+    entries.  With several ranks every file name carries the rank.  Compare values with a tolerance: the element kernels add contributions
+    with LDS atomics, so an entry may differ in its last bit from run to run.'''
+    import numpy
+    import torch
+    from nutils_amd import device
+    os.makedirs(out_dir, exist_ok=True)
+    values, rowptr = wl.values, wl.rowptr.to(torch.int64)
+    nnz, size = values.numel(), DUMP_ENTRIES // world
+    pos = numpy.arange(nnz) if nnz <= size else numpy.sort(numpy.random.default_rng(0).choice(nnz, size, replace=False))
+    idx = torch.from_numpy(pos).to(values.device)
+    out = {'values': values[idx], 'rows': torch.searchsorted(rowptr, idx, right=True) - 1, 'cols': wl.colidx[idx],
+           'summary': torch.tensor([rowptr.numel() - 1, nnz] + [float(x) for x in (values.abs().sum(), values.abs().max(), values.norm())], dtype=torch.float64)}
+    prefix = f'rank{rank}_' if world > 1 else ''
+    for name, t in out.items():
+        numpy.save(os.path.join(out_dir, prefix + name + '.npy'), device.to_host(t.to(torch.float64)))
+
+
 def c3_roofline(wl, kernel_ms, traffic):
     """configs[2]: the kernel writes 37 kB of CSR values per element once -- it is priced against the HBM peak (the write stream is its floor:
     9.7 GB / ~6 TB/s); the matrix-pipe share rides along."""
@@ -403,6 +431,8 @@ def main():
 
     # size-independent check of the assembled matrix on every rank (rows it owns are complete after the interface reduce)
     wl.finish()
+    if a.dump_outputs:
+        dump_outputs(wl, a.dump_outputs, rank, world)
     checks = wl.check(world, dist)
     bad = [k for k, v in checks.items() if not v < 1e-10]
     if bad:
