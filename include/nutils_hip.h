@@ -118,6 +118,10 @@ int nh_pattern_fused_info(const nh_pattern *p, int *nblocks, int *rows_per_block
 /* row tasks of NH_MATRIX_FUSED for vector-valued blocks built for this pattern so far (nh_owner.hip): row blocks (0: none yet, or the plan does not
  * apply), node rows per block, element visits of all blocks, chunks of 64 contributions */
 int nh_pattern_owner_info(const nh_pattern *p, int *nblocks, int *rows_per_block, int64_t *nvisits, int64_t *nchunks);
+/* The owner plan of vector-valued blocks keeps the vertex numbers of its visiting elements, made from the connectivity of an isoparametric geometry and
+ * keyed on the address of that array.  After the array was refilled at the same address, this marks them stale: the next NH_MATRIX_FUSED launch remakes
+ * them (one kernel on the stream of that launch, no synchronisation). */
+int nh_pattern_forget_connectivity(nh_pattern *p);
 int nh_pattern_expanded_nnz(const nh_pattern *p, int nct, int ncr, const unsigned char *mask, int64_t *nnz);
 int nh_pattern_expand(const nh_pattern *p, int nct, int ncr, const unsigned char *mask, int64_t *rowptr_dev,
                       int64_t *colidx_dev, void *stream);

@@ -221,15 +221,17 @@ __global__ void k_gather_values_2x2(i64 nnz, const unsigned *gptr, const int32_t
 // packed row by row (half the scratch, and rows of a node stay contiguous: the reads of neighbouring entries stay neighbours); entries on and below the diagonal are
 // gathered from them in the order of the map (ascending element: the reference's order), entries above are the transposed copies of their mirrors -- the sum of (c, r) is
 // the sum of (r, c) term by term, so the copy is what a second gather would give.
-__global__ void k_tri_rank(i64 nelems, BasisK test, unsigned char *rank, int *cnt) {
+// An element that holds a dof twice (a periodic axis with fewer elements than functions per axis) gives two nodes one rank: *dup is set and the plan refused.
+__global__ void k_tri_rank(i64 nelems, BasisK test, unsigned char *rank, int *cnt, int *dup) {
   for (i64 e = blockIdx.x; e < nelems; e += gridDim.x) {
     const int nb = test.off ? (int)(test.off[e + 1] - test.off[e]) : test.nb;
     const i64 t0 = test.off ? test.off[e] : e * (i64)test.nb;
     for (int m = threadIdx.x; m < nb; m += blockDim.x) {
       const int dm = test.dofs[t0 + m];
-      int r = 0;
-      for (int j = 0; j < nb; ++j) r += test.dofs[t0 + j] < dm;
+      int r = 0, same = 0;
+      for (int j = 0; j < nb; ++j) r += test.dofs[t0 + j] < dm, same += test.dofs[t0 + j] == dm;
       rank[t0 + m] = (unsigned char)r;
+      if (same > 1) *dup = 1;
     }
     if (threadIdx.x == 0) cnt[e] = nb * (nb + 1) / 2;
   }
@@ -1366,7 +1368,8 @@ int nh_gather_prepare_sym(nh_pattern *p, const nh_basis &test, const int32_t *el
   return NH_OK;
 }
 
-// the maps of the triangular scratch, derived from the gather map (once per pattern); sets p->tri_failed when the pattern does not qualify
+// the maps of the triangular scratch, derived from the gather map (once per pattern); sets p->tri_failed when the pattern does not qualify (not symmetric, or an
+// element holds a dof more than once)
 int nh_gather_prepare_tri(nh_pattern *p, const nh_basis &test, hipStream_t s) {
   if (p->gsrc_tri || p->tri_failed) return NH_OK;
   NH_REQUIRE(p->gsrc && p->gptr && p->grow, "nh_gather_prepare_tri: the gather map comes first");
@@ -1394,7 +1397,7 @@ int nh_gather_prepare_tri(nh_pattern *p, const nh_basis &test, hipStream_t s) {
   if (e == hipSuccess) e = hipMalloc((void **)&bad, sizeof(int));
   if (e == hipSuccess) e = hipMemsetAsync(bad, 0, sizeof(int), s);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_tri_rank, dim3((unsigned)std::min<i64>(p->nelems, 1 << 20)), dim3(64), 0, s, p->nelems, tk, p->tri_rank, cnt);
+    hipLaunchKernelGGL(k_tri_rank, dim3((unsigned)std::min<i64>(p->nelems, 1 << 20)), dim3(64), 0, s, p->nelems, tk, p->tri_rank, cnt, bad);
     rc = nh_scan_exclusive(cnt, p->tri_base, p->nelems, s);
   }
   if (e == hipSuccess && rc == NH_OK) {
@@ -1416,7 +1419,7 @@ int nh_gather_prepare_tri(nh_pattern *p, const nh_basis &test, hipStream_t s) {
       nh_set_error("nh_gather_prepare_tri failed: %s", hipGetErrorString(e));
       return NH_EHIP;
     }
-    return rc;  // (a pattern that is not symmetric: no plan, no error)
+    return rc;  // (a pattern that is not symmetric, or an element with a repeated dof: no plan, no error -- the full scratch is used)
   }
   return NH_OK;
 }

@@ -453,6 +453,12 @@ int nh_pattern_owner_info(const nh_pattern *p, int *nblocks, int *rows_per_block
   return NH_OK;
 }
 
+int nh_pattern_forget_connectivity(nh_pattern *p) {
+  NH_REQUIRE(p, "nh_pattern_forget_connectivity: NULL pattern");
+  if (p->owner) p->owner->vvert_src = nullptr;  // (vvert stays allocated: refilled from the connectivity of the next launch)
+  return NH_OK;
+}
+
 int nh_pattern_info(const nh_pattern *p, int64_t *nnz_scalar, const int64_t **srowptr_dev, const int32_t **scolidx_dev,
                     const int32_t **emap_dev, int64_t *emap_len, const int64_t **eoff_dev) {
   NH_REQUIRE(p, "nh_pattern_info: NULL pattern");

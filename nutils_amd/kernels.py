@@ -180,6 +180,16 @@ FUSED_DEFAULT = {(3, 8)}
 OWNER_VECTOR = {(3, 8, 3), (2, 4, 2), (2, 9, 2), (3, 27, 3)}
 
 
+def _follow_connectivity(pattern, geom):
+    '''The owner plan of vector-valued blocks keeps the vertex numbers of its visiting elements, made from the connectivity of an isoparametric geometry and
+    keyed on its address (nh_pattern_forget_connectivity).  A tensor refilled in place keeps its address and bumps its version: then they are remade.'''
+    gdofs = getattr(geom, '_keep', (None, None))[1] if geom.kind == _lib.GEOM_ISO else None
+    key = None if gdofs is None else (gdofs.data_ptr(), gdofs._version)
+    if getattr(pattern, '_connectivity', key) != key:
+        _lib.call('nh_pattern_forget_connectivity', pattern._handle)
+    pattern._connectivity = key
+
+
 def assemble_matrix(*, nelems, ndims, nq, weights, geom, test, trial, nct, ncr, C, mask, pattern, values, elist=None, emap_offset=0, scale=None, flags=0,
                     cq=None, first_touch=None, gather=None, store=False, fused=False, fresh=False):
     '''K3+K4+K5 (nh_assemble_matrix); accumulates into `values`.  `first_touch=(grid_shape, nodes_per_axis)`: NH_MATRIX_FIRST_TOUCH.
@@ -191,6 +201,7 @@ def assemble_matrix(*, nelems, ndims, nq, weights, geom, test, trial, nct, ncr, 
     C = numpy.ascontiguousarray(C, dtype=float)
     if C.shape != (nct, 1 + ndims, ncr, 1 + ndims):
         raise ValueError(f'coefficient tensor has shape {C.shape}, expected {(nct, 1 + ndims, ncr, 1 + ndims)}')
+    _follow_connectivity(pattern, geom)
     m = None if mask is None else numpy.ascontiguousarray(mask, dtype=numpy.uint8)
     if cq is not None and cq.numel() != nelems * nq * C.size:
         raise ValueError('per-point coefficient tensor must have shape [nelems][nq] + C.shape')

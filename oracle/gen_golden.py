@@ -150,16 +150,18 @@ def singular_case(name, coords, seed=9):
     save(name, **data)
 
 
-def elasticity_case(name, shape, degree, iso, poisson=.3, seed=1):
+def elasticity_case(name, shape, degree, iso, poisson=.3, seed=1, periodic=()):
     '''Linear elasticity as in examples/elasticity.py:46-54 (lambda = 1,
     mu = .5/poisson - 1), vector field with ndims components interleaved
     (flat dof = iscalar * ncomp + comp, function.py:2598-2627).'''
     rng = numpy.random.default_rng(seed)
     nd = len(shape)
-    domain, geom0 = mesh.rectilinear(list(shape))
+    domain, geom0 = mesh.rectilinear(list(shape), periodic=periodic)
     nelems = len(domain)
     data = dict(shape=numpy.array(shape), degree=degree, iso=int(iso), lam=1., mu=.5 / poisson - 1)
-    gbasis = domain.basis('std', degree=1)
+    if periodic:
+        data['periodic'] = numpy.array(periodic)
+    gbasis = domain.basis('std', degree=1) if not periodic else None  # (periodic: the geometry is the non-periodic rectilinear map)
     if iso:
         verts = perturbed(shape, rng)
         geom = gbasis @ verts
@@ -561,6 +563,16 @@ def generate_all():
     scalar_case('lap2d_spline2_5x4_per0', (5, 4), 'spline', 2, iso=False, periodic=(0,))
     scalar_case('lap2d_p2_4x3_per1', (4, 3), 'std', 2, iso=False, periodic=(1,))
     scalar_case('lap3d_p1_345_per02', (3, 4, 5), 'std', 1, iso=False, periodic=(0, 2))
+    # periodic axes with fewer elements than functions per axis: an element holds the same dof more than once (or, lap3d_p1_222_per012, its
+    # neighbours on both sides are one element)
+    scalar_case('lap2d_p1_1x3_per0', (1, 3), 'std', 1, iso=False, periodic=(0,))
+    scalar_case('lap2d_spline2_2x3_per0', (2, 3), 'spline', 2, iso=False, periodic=(0,))
+    scalar_case('lap2d_spline2_1x2_per0', (1, 2), 'spline', 2, iso=False, periodic=(0,))
+    scalar_case('lap2d_p1_1x1_per01', (1, 1), 'std', 1, iso=False, periodic=(0, 1))
+    scalar_case('lap2d_spline3_2x2_per01', (2, 2), 'spline', 3, iso=False, periodic=(0, 1))
+    scalar_case('lap3d_p1_122_per012', (1, 2, 2), 'std', 1, iso=False, periodic=(0, 1, 2))
+    scalar_case('lap3d_p1_222_per012', (2, 2, 2), 'std', 1, iso=False, periodic=(0, 1, 2))
+    scalar_case('lap1d_spline3_2_per0', (2,), 'spline', 3, iso=False, periodic=(0,))
     singular_case('lap2d_p1_singular', [numpy.array([0., 1., 1., 2.5]), numpy.array([0., .5, 2.])])
     singular_case('lap3d_p1_singular', [numpy.array([0., 1., 3.]), numpy.array([0., .5, .5, 2.]), numpy.array([0., 1., 1.5])])
     elasticity_case('elast2d_p1_3x3', (3, 3), 1, iso=False)
@@ -568,6 +580,8 @@ def generate_all():
     elasticity_case('elast3d_p1_2_iso', (2, 2, 2), 1, iso=True)
     elasticity_case('elast3d_p2_2', (2, 2, 2), 2, iso=False)
     elasticity_case('elast3d_p2_2_iso', (2, 2, 2), 2, iso=True)
+    elasticity_case('elast2d_p1_1x3_per0', (1, 3), 1, iso=False, periodic=(0,))  # (repeated dofs within an element, as above)
+    elasticity_case('elast2d_p2_2x2_per0', (2, 2), 2, iso=False, periodic=(0,))
     cahnhilliard_case('cahnhilliard_p2_4', 4)
     nurbs_case('nurbs_plate_r2')
     hierarchical_p3_case('hier_thspline3_2d_l4')

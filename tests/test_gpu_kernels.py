@@ -13,8 +13,12 @@ RTOL = 1e-13
 SCALAR = ['lap1d_p1_5', 'lap2d_p1_4x4', 'lap2d_p1_4x3_iso', 'lap2d_p2_3x4_iso', 'lap2d_spline2_4x4', 'lap2d_spline2_5x4_iso',
           'lap3d_p1_2', 'lap3d_p1_3', 'lap3d_p1_4', 'lap3d_p1_234', 'lap3d_p1_3_iso', 'lap3d_p1_543_iso', 'lap3d_p2_2_iso',
           'lap3d_spline2_3_iso', 'lap3d_spline3_3',
-          'lap1d_spline3_6_per0', 'lap2d_spline2_5x4_per0', 'lap2d_p2_4x3_per1', 'lap3d_p1_345_per02']  # (last row: periodic axes)
-ELAST = ['elast2d_p1_3x3', 'elast2d_p2_3x2_iso', 'elast3d_p1_2_iso', 'elast3d_p2_2', 'elast3d_p2_2_iso']
+          'lap1d_spline3_6_per0', 'lap2d_spline2_5x4_per0', 'lap2d_p2_4x3_per1', 'lap3d_p1_345_per02',  # (periodic axes)
+          'lap2d_p1_1x3_per0', 'lap2d_spline2_2x3_per0', 'lap2d_spline2_1x2_per0', 'lap2d_spline3_2x2_per01',
+          'lap3d_p1_122_per012', 'lap3d_p1_222_per012', 'lap1d_spline3_2_per0']  # (periodic, fewer elements than functions per axis: repeated dofs)
+ELAST = ['elast2d_p1_3x3', 'elast2d_p2_3x2_iso', 'elast3d_p1_2_iso', 'elast3d_p2_2', 'elast3d_p2_2_iso',
+         'elast2d_p1_1x3_per0', 'elast2d_p2_2x2_per0']  # (last row: periodic, repeated dofs)
+# (lap2d_p1_1x1_per01, a single constant function whose stiffness entry is rounding noise, is not in SCALAR: tests/test_gpu_repeated_dofs.py covers it)
 
 
 def close(a, b, scale=None):
