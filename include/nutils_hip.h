@@ -497,6 +497,45 @@ int nh_p2hex_rows_uniform(const int *shape, int ncomp, const double *cell_values
  * colidx_dev int64[nh_p2hex_rowptr(shape, nnodes) * ncomp^2]; equal to nh_pattern_build + nh_pattern_expand for this basis */
 int nh_p2hex_pattern(const int *shape, int ncomp, int64_t *rowptr_dev, int64_t *colidx_dev, void *stream);
 
+/* ---- fast path: structured 2-D tensor-product bases on quadrilaterals, constant-coefficient forms, scalar or vector valued ---------
+ * Same result (within rounding) as nh_pattern_* + nh_assemble_matrix for the 'std' basis of degree 1 or 2 and the 'spline' basis of degree 2
+ * (StructuredBasis function.py:3030-3100, no periodic axis) of a full 2-D structured topology, test = trial basis with ncomp components and
+ * all ncomp x ncomp blocks present, a constant tensor C (examples/laplace.py, poisson.py, elasticity.py), but WRITE-ONCE: a workgroup owns a
+ * tile of node lines x nodes, evaluates the geometry of every element touching it into LDS, forms each of its rows in the registers of one
+ * lane, and streams the tile's rows -- contiguous in the value array, one segment per line -- with coalesced stores.  No global atomics, no
+ * zero-fill, no element map; repeated calls are bit-identical.
+ * Pattern (closed form): per axis with n elements, 'std' degree p: dof X couples to [X-p, X+p] if X % p == 0, else to [p (X/p), p (X/p) + p],
+ * clipped to [0, n p]; 'spline': to [max(0, X-p), min(n+p-1, X+p)]; a row is the Kronecker product of the two ranges (axis 0 slowest),
+ * components as in nh_pattern_expand.  btype: 0 = 'std', 1 = 'spline'.  nh_quad_nnz is a host computation (no device). */
+typedef struct {
+  int shape[2];
+  int btype, degree;         /* ('std', 1), ('std', 2), ('spline', 2) */
+  int nq;
+  const double *weights_dev; /* [nq] */
+  nh_geometry geom;          /* ISO: gT_dev = the bilinear 'std' table [4][nq][3], verts_dev [(n0+1)(n1+1)][2] (vertex (i, j) at i (n1+1) + j; gdofs_dev
+                                unused); BOX: size_dev [nelems][2] (element index last axis fastest).  bnd_axis must be -1. */
+  const double *T_dev;       /* [nclass0 * nclass1][(p+1)^2][nq][3]: tabulated functions of every element class (class = c0 * nclass1 + c1) */
+  int nclass[2];             /* classes per axis (StructuredBasis.nclasses_axis) */
+  const int32_t *class0_dev, *class1_dev; /* per-axis class of every element (StructuredBasis.axis_class); may be NULL for an axis of one class */
+  int ncomp;                 /* 1 or 2 */
+  const double *C_host;      /* [ncomp][3][ncomp][3] (host memory) */
+  double *values_dev;        /* [nh_quad_nnz] */
+  int max_workgroups;        /* 0: one workgroup per tile; > 0: at most that many (they stride over the tiles) */
+} nh_quad_args;
+
+int nh_quad_nnz(const int *shape, int btype, int degree, int ncomp, int64_t *nnz);
+/* rowptr_dev int64[ndofs * ncomp + 1], colidx_dev int64[nh_quad_nnz]; equal to nh_pattern_build + nh_pattern_expand (all blocks) */
+int nh_quad_pattern(const int *shape, int btype, int degree, int ncomp, int64_t *rowptr_dev, int64_t *colidx_dev, void *stream);
+/* values of the form; NH_ELIMIT when the geometric factors of a tile do not fit the LDS (too many quadrature points): use nh_assemble_matrix */
+int nh_quad_matrix(const nh_quad_args *args, void *stream);
+/* Meshes of UNIFORM cells (equidistant rectilinear vertices), constant form: the rows of a dof depend only on its place per axis (head, one
+ * period of the interior, tail), all of which a small mesh holds -- 2 elements per axis for 'std', 3p-1 for splines (fewer when the mesh is
+ * smaller: then it is the mesh).  nh_quad_uniform_shape gives that shape; small_values_dev: nh_quad_matrix on the small mesh of the same cells
+ * (classes of the first / last elements per axis as in the big mesh); nh_quad_rows_uniform replicates its rows into values_dev: a pure write
+ * stream with the layout of nh_quad_matrix. */
+int nh_quad_uniform_shape(const int *shape, int btype, int degree, int *small_shape);
+int nh_quad_rows_uniform(const int *shape, int btype, int degree, int ncomp, const double *small_values_dev, double *values_dev, void *stream);
+
 /* ---- Monomial: evaluation of factored (pre-integrated) polynomial functionals -------------
  * replaces evaluable.Monomial (evaluable.py:5693-5751; `out = values.copy(); out *= arg[index]`
  * + Inflate/add.at), the per-Newton-step work after evaluable.factor (evaluable.py:5785-5874)

@@ -111,6 +111,12 @@ class P2HexArgs(ctypes.Structure):
                 ('owner_begin', ctypes.c_int), ('owner_end', ctypes.c_int), ('max_workgroups', ctypes.c_int), ('weights_positive', ctypes.c_int)]
 
 
+class QuadArgs(ctypes.Structure):
+    _fields_ = [('shape', ctypes.c_int * 2), ('btype', ctypes.c_int), ('degree', ctypes.c_int), ('nq', ctypes.c_int), ('weights_dev', vp), ('geom', Geometry),
+                ('T_dev', vp), ('nclass', ctypes.c_int * 2), ('class0_dev', vp), ('class1_dev', vp), ('ncomp', ctypes.c_int), ('C_host', vp),
+                ('values_dev', vp), ('max_workgroups', ctypes.c_int)]
+
+
 GEOM_ISO = 1
 GEOM_BOX = 2
 GEOM_TAB = 3
@@ -169,6 +175,11 @@ SIGNATURES = {
     'nh_p2hex_rowptr': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), c_i64, c_i64p]),
     'nh_p2hex_rows_uniform': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, vp]),
     'nh_p1hex_unit_matrix': (ctypes.c_int, [ctypes.POINTER(P1HexArgs), vp, vp]),
+    'nh_quad_nnz': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i64p]),
+    'nh_quad_pattern': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp]),
+    'nh_quad_matrix': (ctypes.c_int, [ctypes.POINTER(QuadArgs), vp]),
+    'nh_quad_uniform_shape': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
+    'nh_quad_rows_uniform': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp]),
 }
 
 _lib = None

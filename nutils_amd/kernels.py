@@ -659,3 +659,86 @@ def point_forms(kind, Ut, B, Ur=None, L=None, scale=None):
     _lib.call('nh_point_forms', kind, n, S, device.ptr(Ut), device.ptr(Ur) if Ur is not None else None, Bc, Lc,
               device.ptr(scale) if scale is not None else None, device.ptr(out), device.stream())
     return out
+
+
+QUAD_BTYPES = {'std': 0, 'spline': 1}
+
+
+def quad_nnz(shape, btype, degree, ncomp):
+    '''Entries of the closed-form CSR of a structured 2-D basis with ncomp fully coupled components (nh_quad_nnz: host only, no device).'''
+    out = ctypes.c_int64()
+    _lib.call('nh_quad_nnz', (ctypes.c_int * 2)(*[int(n) for n in shape]), QUAD_BTYPES[btype], int(degree), int(ncomp), ctypes.byref(out))
+    return out.value
+
+
+def quad_pattern(shape, btype, degree, ncomp):
+    '''Closed-form CSR index arrays of the structured 2-D 'std' / 'spline' basis with ncomp fully coupled components (nh_quad_pattern).'''
+    n0, n1 = (int(n) for n in shape)
+    ndofs = (n0 + degree, n1 + degree) if btype == 'spline' else (n0 * degree + 1, n1 * degree + 1)
+    rowptr = device.empty(ndofs[0] * ndofs[1] * ncomp + 1, 'int64')
+    colidx = device.empty(quad_nnz(shape, btype, degree, ncomp), 'int64')
+    _lib.call('nh_quad_pattern', (ctypes.c_int * 2)(n0, n1), QUAD_BTYPES[btype], int(degree), int(ncomp), device.ptr(rowptr), device.ptr(colidx), device.stream())
+    return rowptr, colidx
+
+
+class QuadMatrix:
+    '''Write-once assembly of a constant-coefficient form on a structured 2-D basis (nh_quad_matrix), argument block filled once: a re-assembly is one
+    ctypes call.  T: the class tables [nclass][nb][nq][3]; classes: the per-axis class arrays (StructuredBasis.axis_class), host.  Call with the value
+    array of the step.'''
+
+    def __init__(self, *, shape, btype, degree, nq, weights, geom, T, classes, ncomp, C, max_workgroups=0):
+        C = numpy.ascontiguousarray(C, dtype=float)
+        if C.shape != (ncomp, 3, ncomp, 3):
+            raise ValueError(f'coefficient tensor has shape {C.shape}, expected {(ncomp, 3, ncomp, 3)}')
+        a = _lib.QuadArgs()
+        a.shape[:] = [int(n) for n in shape]
+        a.btype, a.degree, a.nq = QUAD_BTYPES[btype], int(degree), int(nq)
+        a.weights_dev = device.ptr(weights)
+        a.geom = geom
+        a.T_dev = device.ptr(T)
+        ncls = [int(numpy.max(c)) + 1 for c in classes]
+        cls = [device.to_dev(numpy.asarray(c, dtype=numpy.int32), 'int32') if n > 1 else None for c, n in zip(classes, ncls)]
+        a.nclass[:] = ncls
+        a.class0_dev, a.class1_dev = device.ptr(cls[0]), device.ptr(cls[1])
+        a.ncomp = int(ncomp)
+        a.C_host = device.host_ptr(C)
+        a.max_workgroups = int(max_workgroups)
+        self._keep = (weights, geom, T, C, cls)
+        self._args = a
+        self._ref = ctypes.byref(a)
+        self._name = 'nh_quad_matrix'
+        self._fn = getattr(_lib.load(), self._name)
+
+    def __call__(self, values):
+        self._args.values_dev = values.data_ptr()
+        if _lib.TRACE is not None:
+            _lib.TRACE.append(self._name)
+        _lib.check(self._fn(self._ref, device.stream()))
+
+
+class QuadUniform:
+    '''The same matrix on a mesh of UNIFORM cells (`cell`: the two edge lengths): the small mesh of nh_quad_uniform_shape of such cells is assembled once by
+    nh_quad_matrix (its first and last elements per axis take the classes of the big mesh's), a (re-)assembly replicates its rows (nh_quad_rows_uniform).'''
+
+    def __init__(self, *, shape, btype, degree, nq, weights, T, classes, ncomp, C, cell):
+        small = (ctypes.c_int * 2)()
+        self._shape = (ctypes.c_int * 2)(*[int(n) for n in shape])
+        _lib.call('nh_quad_uniform_shape', self._shape, QUAD_BTYPES[btype], int(degree), small)
+        small = tuple(small)
+        cls = []
+        for n, ns, c in zip(shape, small, classes):
+            es = numpy.arange(ns)
+            cls.append(numpy.asarray(c)[numpy.where(es <= ns // 2, es, es - ns + int(n))])
+        idx = numpy.stack(numpy.meshgrid(*[numpy.arange(float(n)) for n in small], indexing='ij'), -1).reshape(-1, 2)
+        cell = numpy.asarray(cell, dtype=float).reshape(2)
+        geom = geometry_box(device.to_dev(idx * cell, 'float64'), device.to_dev(numpy.broadcast_to(cell, idx.shape), 'float64'))
+        self.table = device.empty(quad_nnz(small, btype, degree, ncomp), 'float64')
+        QuadMatrix(shape=small, btype=btype, degree=degree, nq=nq, weights=weights, geom=geom, T=T, classes=cls, ncomp=ncomp, C=C)(self.table)
+        self._bt, self._deg, self._nc = QUAD_BTYPES[btype], int(degree), int(ncomp)
+        self._name = 'nh_quad_rows_uniform'
+        self._fn = getattr(_lib.load(), self._name)
+
+    def __call__(self, values):
+        if _lib.TRACE is not None:
+            _lib.TRACE.append(self._name)
+        _lib.check(self._fn(self._shape, self._bt, self._deg, self._nc, self.table.data_ptr(), values.data_ptr(), device.stream()))

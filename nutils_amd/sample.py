@@ -700,6 +700,53 @@ class _MatrixPlan:
         fn(values)
         return values
 
+    def _quad(self):
+        '''Constant-coefficient forms on a structured 2-D basis (bilinear, biquadratic, quadratic spline; scalar or two components) go to the
+        write-once kernel nh_quad_matrix (or, on equidistant rectilinear cells, nh_quad_rows_uniform) with the closed-form pattern of
+        nh_quad_pattern: no sort, no element map, no zero-fill.  Returns (values, rowptr, colidx, ncols), or None when _quad_form declines
+        (then the generic path assembles the integral).'''
+        setting = _quad_form(self)
+        if setting is None:
+            return None
+        C, geom, mode = setting
+        basis, smp, nc = self.test.basis, self.smp0, self.test.ncomp
+        key = 'quad_pattern', basis.shape, basis.btype, basis.degree, nc
+        if key not in smp._tables:
+            smp._tables[key] = kernels.quad_pattern(basis.shape, basis.btype, basis.degree, nc)
+        rowptr, colidx = smp._tables[key]
+        # launchers by geometry OBJECT, then by form (the bounds of _p2hex)
+        if not hasattr(smp, '_quad_fns'):
+            smp._quad_fns = {}
+        by_form = _cached(smp._quad_fns, geom, dict)
+        # (one sample serves every basis integrated at its points: the basis and the components belong to the key, or a launcher of another basis -- its
+        # shape, tables and value count -- would be reused)
+        key = (basis.btype, basis.degree, basis.shape, nc, mode, C.tobytes())
+        if len(by_form) >= 8 and key not in by_form:
+            by_form.pop(next(iter(by_form)))
+        fn = by_form.get(key)
+        fresh = None
+        if fn is None:
+            common = dict(shape=basis.shape, btype=basis.btype, degree=basis.degree, nq=smp.points.npoints, weights=smp._weights_dev, T=smp.tables(basis).T,
+                          classes=basis.axis_class, ncomp=nc, C=C)
+            try:
+                if mode == 'uniform':  # equidistant vertices: the rows of a small mesh of such cells, replicated (a write stream)
+                    fn = kernels.QuadUniform(cell=geom.scale, **common)
+                else:
+                    fn = kernels.QuadMatrix(geom=smp.geometry(geom), **common)
+                fresh = device.empty(colidx.numel(), 'float64')
+                fn(fresh)  # NH_ELIMIT (the factors of a tile do not fit the LDS for this quadrature) surfaces here
+            except _lib_error() as e:
+                if 'LDS' not in str(e):
+                    raise
+                fn = False
+            by_form[key] = fn
+        if fn is False:
+            return None
+        if fresh is None:
+            fresh = device.empty(colidx.numel(), 'float64')
+            fn(fresh)
+        return fresh, rowptr, colidx, basis.ndofs * nc
+
     def _first_touch(self, term):
         '''(elements per axis, local nodes per axis) if the first term is assembled colour by colour on a non-periodic C0 ('std') basis
         whose local order is the tensor order of its nodes: NH_MATRIX_FIRST_TOUCH applies.'''
@@ -863,6 +910,9 @@ class _MatrixPlan:
         fast = self._p1hex_laplace(arguments)
         if fast is not None and not fast[4]:
             return fast[:4]
+        quad = self._quad()
+        if quad is not None:
+            return quad
         pat = self.smp0.pattern(self.test.basis, self.trial.basis)
         nct, ncr = self.test.ncomp, self.trial.ncomp
         mask = None if self.mask.all() else self.mask
@@ -957,6 +1007,52 @@ class _MatrixPlan:
         if fresh[0]:  # (no term at all)
             values.zero_()
         return values, rowptr, colidx, self.trial.basis.ndofs * ncr
+
+
+QUAD_BASES = (('std', 1), ('std', 2), ('spline', 2))
+# Bases whose NON-uniform cells (isoparametric or graded geometry) the front end routes to nh_quad_matrix: measured on one MI355X (profiles/quad_write_once.md) the
+# kernel beats the generic path there for the bilinear basis only; biquadratic and spline meshes keep the generic path unless their cells are equidistant
+# (nh_quad_rows_uniform).  nh_quad_matrix itself takes all three bases on any geometry (it builds the small meshes of the uniform path).
+QUAD_GEOMETRIC_BASES = (('std', 1),)
+
+
+def _quad_form(plan):
+    '''The host-side decision of _MatrixPlan._quad: (summed form tensor C [nc][3][nc][3], geometry, mode) if the plan is in the class of nh_quad_matrix,
+    else None.  Mode 'iso' (isoparametric bilinear map), 'box' (axis-aligned cells: graded meshes, or rectilinear ones with NUTILS_AMD_NO_UNIFORM) or
+    'uniform' (equidistant rectilinear cells: nh_quad_rows_uniform).  Needs no device.'''
+    if plan.parts is not None or os.environ.get('NUTILS_AMD_NO_FAST_PATH'):
+        return None
+    basis, smp, nc = plan.test.basis, plan.smp0, plan.test.ncomp
+    if not (basis is plan.trial.basis and isinstance(basis, StructuredBasis) and basis.ndims == 2 and (basis.btype, basis.degree) in QUAD_BASES
+            and nc == plan.trial.ncomp and nc in (1, 2) and plan.mask.all() and not basis.periodic):
+        return None
+    p = basis.degree
+    if basis.dofs_shape != tuple(n + p if basis.btype == 'spline' else n * p + 1 for n in basis.shape):
+        return None  # (periodic axis)
+    if smp.elist is not None or smp.bnd_axis >= 0:
+        return None
+    C, geom = 0., None
+    for _, itg, fac in plan.terms:
+        if not (itg.qform is None and itg.qscalar is None and itg.scale is None and itg.fscale is None and not getattr(itg, 'pvars', ()) and itg.measure is not None
+                and numpy.shape(itg.B) == (nc, 3, nc, 3) and (geom is None or itg.measure is geom)):
+            return None
+        geom = itg.measure
+        C = C + numpy.asarray(itg.B, dtype=float) * fac
+    if (basis.btype, basis.degree) not in QUAD_GEOMETRIC_BASES and not (isinstance(geom, function.RectilinearGeometry) and not os.environ.get('NUTILS_AMD_NO_UNIFORM')):
+        return None
+    if isinstance(geom, function.IsoGeometry):
+        g = geom.basis
+        if not (isinstance(g, StructuredBasis) and g.btype == 'std' and g.degree == 1 and g.shape == basis.shape and not g.periodic
+                and g.dofs_shape == tuple(n + 1 for n in basis.shape)):
+            return None
+        mode = 'iso'
+    elif isinstance(geom, function.RectilinearGeometry) and tuple(geom.topo.shape) == basis.shape:
+        mode = 'box' if os.environ.get('NUTILS_AMD_NO_UNIFORM') else 'uniform'
+    elif isinstance(geom, function.GradedGeometry) and tuple(geom.topo.shape) == basis.shape and geom.size.all():
+        mode = 'box'  # (axis-aligned cells, J = diag(size); flat cells: generic path, NaN rules of numeric.inv)
+    else:
+        return None
+    return numpy.ascontiguousarray(C), geom, mode
 
 
 def _rectilinear_vertices(geom, shape):

@@ -313,3 +313,23 @@ class ElasticityP2:
     def owned_csr(self):
         '''(values, rowptr, colidx) of the rows this rank owns, global numbering, on the host.'''
         return partition.owned_rows(self.slab, device.to_host(self.values), device.to_host(self.rowptr), device.to_host(self.colidx))
+
+
+def quad_form(shape, btype, degree, nc, uniform=False, seed=0):
+    '''The 2-D matrix integrals of tools/quad_probe.py and tools/generic_probe.py: Laplace (nc = 1) or linear elasticity (nc = 2, lambda = 1, 2 mu = 1.3) on
+    a structured quadrilateral mesh, Gauss degree 2 p; geometry: the isoparametric P1 map of the unit grid with vertices perturbed by up to 0.2, or
+    (uniform) the equidistant rectilinear cells.'''
+    domain, geom = mesh.rectilinear(list(shape))
+    if not uniform:
+        rng = numpy.random.default_rng(seed)
+        verts = numpy.stack(numpy.meshgrid(*[numpy.arange(n + 1.) for n in shape], indexing='ij'), -1).reshape(-1, 2)
+        geom = domain.basis('std', degree=1) @ (verts + rng.uniform(-.2, .2, verts.shape))
+    dV = function.J(geom)
+    if nc == 1:
+        basis = domain.basis(btype, degree=degree)
+        return domain.integral(function.outer(function.grad(basis, geom)).sum(-1) * dV, degree=2 * degree)
+    u = domain.field('u', btype=btype, degree=degree, shape=[2])
+    v = domain.field('v', btype=btype, degree=degree, shape=[2])
+    eps = lambda w: function.symgrad(w, geom)
+    res = domain.integral(function.inner(eps(v), function.div(u, geom) * function.eye(2) + 1.3 * eps(u)) * dV, degree=2 * degree)
+    return function.derivative(function.derivative(res, 'v'), 'u')
