@@ -536,6 +536,37 @@ int nh_quad_matrix(const nh_quad_args *args, void *stream);
 int nh_quad_uniform_shape(const int *shape, int btype, int degree, int *small_shape);
 int nh_quad_rows_uniform(const int *shape, int btype, int degree, int ncomp, const double *small_values_dev, double *values_dev, void *stream);
 
+/* ---- fast path: the trilinear 'std' basis of a full 3-D structured topology, constant-coefficient forms, 1-3 components -------------------
+ * Same result (within rounding) as nh_pattern_* + nh_assemble_matrix for the 'std' basis of degree 1 (no periodic axis), test = trial basis
+ * with ncomp components and all ncomp x ncomp blocks present, a constant tensor C (3-D linear elasticity, anisotropic diffusion), but
+ * WRITE-ONCE: a workgroup owns a column of 2 x 2 nodes over a chunk of node planes, forms the Gram G_mn = sum_q w|J| D_m D_n^T of every element
+ * under it (one element layer at a time, in LDS), sums the Grams of the elements that share a node pair in a fixed order, applies C and streams
+ * the rows out with coalesced stores.  No global atomics, no zero-fill, no element map; repeated calls are bit-identical.
+ * Pattern (closed form): node X of an axis with N = n + 1 nodes couples to [max(0, X-1), min(N-1, X+1)]; a row is the Kronecker product of the
+ * three ranges (axis 0 slowest), components as in nh_pattern_expand.  nh_hex1_nnz is a host computation (no device). */
+typedef struct {
+  int shape[3];
+  int nq;
+  const double *weights_dev; /* [nq] */
+  nh_geometry geom;          /* ISO: verts_dev [(n0+1)(n1+1)(n2+1)][3] (lexicographic; the map is the basis itself, T_dev serves as its table: gT_dev,
+                                gdofs_dev unused);
+                                BOX: size_dev [nelems][3] (element index last axis fastest).  bnd_axis must be -1. */
+  const double *T_dev;       /* [8][nq][4]: tabulated functions of the basis */
+  int ncomp;                 /* 1, 2 or 3 */
+  const double *C_host;      /* [ncomp][4][ncomp][4] (host memory) */
+  double *values_dev;        /* [nh_hex1_nnz] */
+} nh_hex1_args;
+
+int nh_hex1_nnz(const int *shape, int ncomp, int64_t *nnz);
+/* rowptr_dev int64[(n0+1)(n1+1)(n2+1) ncomp + 1], colidx_dev int64[nh_hex1_nnz]; equal to nh_pattern_build + nh_pattern_expand (all blocks) */
+int nh_hex1_pattern(const int *shape, int ncomp, int64_t *rowptr_dev, int64_t *colidx_dev, void *stream);
+/* values of the form; NH_ELIMIT when the tables of the quadrature do not fit the LDS: use nh_assemble_matrix */
+int nh_hex1_matrix(const nh_hex1_args *args, void *stream);
+/* Meshes of UNIFORM cells (equidistant rectilinear vertices), constant form: the rows of a node depend only on its class per axis (first,
+ * interior, last), all of which the mesh of min(n, 2) elements per axis holds.  small_values_dev: nh_hex1_matrix on that mesh of the same
+ * cells; nh_hex1_rows_uniform replicates its rows into values_dev: a pure write stream with the layout of nh_hex1_matrix. */
+int nh_hex1_rows_uniform(const int *shape, int ncomp, const double *small_values_dev, double *values_dev, void *stream);
+
 /* ---- Monomial: evaluation of factored (pre-integrated) polynomial functionals -------------
  * replaces evaluable.Monomial (evaluable.py:5693-5751; `out = values.copy(); out *= arg[index]`
  * + Inflate/add.at), the per-Newton-step work after evaluable.factor (evaluable.py:5785-5874)

@@ -117,6 +117,11 @@ class QuadArgs(ctypes.Structure):
                 ('values_dev', vp), ('max_workgroups', ctypes.c_int)]
 
 
+class Hex1Args(ctypes.Structure):
+    _fields_ = [('shape', ctypes.c_int * 3), ('nq', ctypes.c_int), ('weights_dev', vp), ('geom', Geometry), ('T_dev', vp), ('ncomp', ctypes.c_int),
+                ('C_host', vp), ('values_dev', vp)]
+
+
 GEOM_ISO = 1
 GEOM_BOX = 2
 GEOM_TAB = 3
@@ -180,6 +185,10 @@ SIGNATURES = {
     'nh_quad_matrix': (ctypes.c_int, [ctypes.POINTER(QuadArgs), vp]),
     'nh_quad_uniform_shape': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     'nh_quad_rows_uniform': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp, vp]),
+    'nh_hex1_nnz': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.c_int, c_i64p]),
+    'nh_hex1_pattern': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.c_int, vp, vp, vp]),
+    'nh_hex1_matrix': (ctypes.c_int, [ctypes.POINTER(Hex1Args), vp]),
+    'nh_hex1_rows_uniform': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.c_int, vp, vp, vp]),
 }
 
 _lib = None

@@ -742,3 +742,72 @@ class QuadUniform:
         if _lib.TRACE is not None:
             _lib.TRACE.append(self._name)
         _lib.check(self._fn(self._shape, self._bt, self._deg, self._nc, self.table.data_ptr(), values.data_ptr(), device.stream()))
+
+
+def hex1_nnz(shape, ncomp):
+    '''Entries of the closed-form CSR of the trilinear 'std' basis of a 3-D structured mesh with ncomp fully coupled components (nh_hex1_nnz: host only,
+    no device).'''
+    out = ctypes.c_int64()
+    _lib.call('nh_hex1_nnz', (ctypes.c_int * 3)(*[int(n) for n in shape]), int(ncomp), ctypes.byref(out))
+    return out.value
+
+
+def hex1_pattern(shape, ncomp):
+    '''Closed-form CSR index arrays of the trilinear 'std' basis of a 3-D structured mesh with ncomp fully coupled components (nh_hex1_pattern).'''
+    shape = [int(n) for n in shape]
+    rowptr = device.empty(int(numpy.prod([n + 1 for n in shape])) * ncomp + 1, 'int64')
+    colidx = device.empty(hex1_nnz(shape, ncomp), 'int64')
+    _lib.call('nh_hex1_pattern', (ctypes.c_int * 3)(*shape), int(ncomp), device.ptr(rowptr), device.ptr(colidx), device.stream())
+    return rowptr, colidx
+
+
+class Hex1Matrix:
+    '''Write-once assembly of a constant-coefficient form on the trilinear 'std' basis of a 3-D structured mesh (nh_hex1_matrix), argument block filled
+    once: a re-assembly is one ctypes call.  T: the basis table [8][nq][4]; geom: an ISO (vertices, lexicographic) or BOX geometry.  Call with the
+    value array of the step.'''
+
+    def __init__(self, *, shape, nq, weights, geom, T, ncomp, C):
+        C = numpy.ascontiguousarray(C, dtype=float)
+        if C.shape != (ncomp, 4, ncomp, 4):
+            raise ValueError(f'coefficient tensor has shape {C.shape}, expected {(ncomp, 4, ncomp, 4)}')
+        a = _lib.Hex1Args()
+        a.shape[:] = [int(n) for n in shape]
+        a.nq = int(nq)
+        a.weights_dev = device.ptr(weights)
+        a.geom = geom
+        a.T_dev = device.ptr(T)
+        a.ncomp = int(ncomp)
+        a.C_host = device.host_ptr(C)
+        self._keep = (weights, geom, T, C)
+        self._args = a
+        self._ref = ctypes.byref(a)
+        self._name = 'nh_hex1_matrix'
+        self._fn = getattr(_lib.load(), self._name)
+
+    def __call__(self, values):
+        self._args.values_dev = values.data_ptr()
+        if _lib.TRACE is not None:
+            _lib.TRACE.append(self._name)
+        _lib.check(self._fn(self._ref, device.stream()))
+
+
+class Hex1Uniform:
+    '''The same matrix on a mesh of UNIFORM cells (`cell`: the three edge lengths): the mesh of min(n, 2) such cells per axis is assembled once by
+    nh_hex1_matrix, a (re-)assembly replicates its rows (nh_hex1_rows_uniform).'''
+
+    def __init__(self, *, shape, nq, weights, T, ncomp, C, cell):
+        small = tuple(min(int(n), 2) for n in shape)
+        self._shape = (ctypes.c_int * 3)(*[int(n) for n in shape])
+        idx = numpy.stack(numpy.meshgrid(*[numpy.arange(float(n)) for n in small], indexing='ij'), -1).reshape(-1, 3)
+        cell = numpy.asarray(cell, dtype=float).reshape(3)
+        geom = geometry_box(device.to_dev(idx * cell, 'float64'), device.to_dev(numpy.broadcast_to(cell, idx.shape), 'float64'))
+        self.table = device.empty(hex1_nnz(small, ncomp), 'float64')
+        Hex1Matrix(shape=small, nq=nq, weights=weights, geom=geom, T=T, ncomp=ncomp, C=C)(self.table)
+        self._nc = int(ncomp)
+        self._name = 'nh_hex1_rows_uniform'
+        self._fn = getattr(_lib.load(), self._name)
+
+    def __call__(self, values):
+        if _lib.TRACE is not None:
+            _lib.TRACE.append(self._name)
+        _lib.check(self._fn(self._shape, self._nc, self.table.data_ptr(), values.data_ptr(), device.stream()))

@@ -747,6 +747,50 @@ class _MatrixPlan:
             fn(fresh)
         return fresh, rowptr, colidx, basis.ndofs * nc
 
+    def _hex1(self):
+        '''Constant-coefficient forms on the trilinear 'std' basis of a full 3-D structured topology with 1-3 components (3-D linear elasticity,
+        anisotropic diffusion) go to the write-once kernel nh_hex1_matrix (or, on equidistant rectilinear cells, nh_hex1_rows_uniform) with the
+        closed-form pattern of nh_hex1_pattern.  Returns (values, rowptr, colidx, ncols), or None when _hex1_form declines (then the generic path
+        assembles the integral).'''
+        setting = _hex1_form(self)
+        if setting is None:
+            return None
+        C, geom, mode = setting
+        basis, smp, nc = self.test.basis, self.smp0, self.test.ncomp
+        key = 'hex1_pattern', basis.shape, nc
+        if key not in smp._tables:
+            smp._tables[key] = kernels.hex1_pattern(basis.shape, nc)
+        rowptr, colidx = smp._tables[key]
+        # launchers by geometry OBJECT, then by form (the bounds of _p2hex and _quad)
+        if not hasattr(smp, '_hex1_fns'):
+            smp._hex1_fns = {}
+        by_form = _cached(smp._hex1_fns, geom, dict)
+        key = (basis.shape, nc, mode, C.tobytes())
+        if len(by_form) >= 8 and key not in by_form:
+            by_form.pop(next(iter(by_form)))
+        fn = by_form.get(key)
+        fresh = None
+        if fn is None:
+            common = dict(shape=basis.shape, nq=smp.points.npoints, weights=smp._weights_dev, T=smp.tables(basis).T, ncomp=nc, C=C)
+            try:
+                if mode == 'uniform':  # equidistant vertices: the rows of the 2 x 2 x 2 mesh of such cells, replicated (a write stream)
+                    fn = kernels.Hex1Uniform(cell=geom.scale, **common)
+                else:
+                    fn = kernels.Hex1Matrix(geom=smp.geometry(geom), **common)
+                fresh = device.empty(colidx.numel(), 'float64')
+                fn(fresh)  # NH_ELIMIT (the tables of this quadrature do not fit the LDS) surfaces here
+            except _lib_error() as e:
+                if 'LDS' not in str(e):
+                    raise
+                fn = False
+            by_form[key] = fn
+        if fn is False:
+            return None
+        if fresh is None:
+            fresh = device.empty(colidx.numel(), 'float64')
+            fn(fresh)
+        return fresh, rowptr, colidx, basis.ndofs * nc
+
     def _first_touch(self, term):
         '''(elements per axis, local nodes per axis) if the first term is assembled colour by colour on a non-periodic C0 ('std') basis
         whose local order is the tensor order of its nodes: NH_MATRIX_FIRST_TOUCH applies.'''
@@ -913,6 +957,10 @@ class _MatrixPlan:
         quad = self._quad()
         if quad is not None:
             return quad
+        if fast is None:
+            hex1 = self._hex1()
+            if hex1 is not None:
+                return hex1
         pat = self.smp0.pattern(self.test.basis, self.trial.basis)
         nct, ncr = self.test.ncomp, self.trial.ncomp
         mask = None if self.mask.all() else self.mask
@@ -1051,6 +1099,66 @@ def _quad_form(plan):
     elif isinstance(geom, function.GradedGeometry) and tuple(geom.topo.shape) == basis.shape and geom.size.all():
         mode = 'box'  # (axis-aligned cells, J = diag(size); flat cells: generic path, NaN rules of numeric.inv)
     else:
+        return None
+    return numpy.ascontiguousarray(C), geom, mode
+
+
+HEX1_MODES = ('iso', 'box', 'uniform')
+HEX1_ALL = tuple((m, nc) for m in HEX1_MODES for nc in (1, 2, 3))
+# (mode, components) that the front end routes to the trilinear write-once path by default: only what beat the generic path in the same process on one
+# MI355X (profiles/hex1_write_once.md) -- equidistant cells with 1 or 3 components (nh_hex1_rows_uniform: 6.5-7.4x for 128^3 anisotropic diffusion, 1.8-2.2x
+# for 96^3 elasticity).  nh_hex1_matrix on isoparametric and graded cells measured 0.14-0.66x of the generic path, so those keep the generic path, and 2
+# components were not measured.  _hex1_form takes every combination when this table is widened to HEX1_ALL (the tests do).
+HEX1_ROUTED = (('uniform', 1), ('uniform', 3))
+
+
+def _p1hex_claims(plan):
+    '''Would _p1hex_laplace take (part of) this constant scalar plan -- a term `(kappa grad . grad + mu) J(geom)`, B = diag(mu, kappa, kappa, kappa)?
+    (Host-only; any Gauss rule: the trilinear write-once path never takes an isotropic scalar form.)'''
+    for _, itg, fac in plan.terms:
+        B = numpy.asarray(itg.B, dtype=float) * fac
+        if B.shape == (1, 4, 1, 4):
+            B = B[0, :, 0, :]
+            if numpy.array_equal(B, numpy.diag([B[0, 0], B[1, 1], B[1, 1], B[1, 1]])):
+                return True
+    return False
+
+
+def _hex1_form(plan):
+    '''The host-side decision of _MatrixPlan._hex1: (summed form tensor C [nc][4][nc][4], geometry, mode) if the plan is in the class of nh_hex1_matrix,
+    else None.  Mode 'iso' (isoparametric trilinear map), 'box' (axis-aligned cells: graded meshes, or rectilinear ones with NUTILS_AMD_NO_UNIFORM) or
+    'uniform' (equidistant rectilinear cells: nh_hex1_rows_uniform).  Scalar forms that the headline path (_p1hex_laplace) takes stay there.  Needs no
+    device.'''
+    if plan.parts is not None or os.environ.get('NUTILS_AMD_NO_FAST_PATH'):
+        return None
+    basis, smp, nc = plan.test.basis, plan.smp0, plan.test.ncomp
+    if not (basis is plan.trial.basis and isinstance(basis, StructuredBasis) and basis.ndims == 3 and basis.btype == 'std' and basis.degree == 1
+            and nc == plan.trial.ncomp and nc in (1, 2, 3) and plan.mask.all() and getattr(basis, 'nclasses', 1) == 1
+            and basis.dofs_shape == tuple(n + 1 for n in basis.shape)):
+        return None
+    if smp.elist is not None or smp.bnd_axis >= 0:
+        return None
+    C, geom = 0., None
+    for _, itg, fac in plan.terms:
+        if not (itg.qform is None and itg.qscalar is None and itg.scale is None and itg.fscale is None and not getattr(itg, 'pvars', ()) and itg.measure is not None
+                and numpy.shape(itg.B) == (nc, 4, nc, 4) and (geom is None or itg.measure is geom)):
+            return None
+        geom = itg.measure
+        C = C + numpy.asarray(itg.B, dtype=float) * fac
+    if nc == 1 and _p1hex_claims(plan):
+        return None
+    if isinstance(geom, function.IsoGeometry):
+        g = geom.basis
+        if not (isinstance(g, StructuredBasis) and g.btype == 'std' and g.degree == 1 and g.shape == basis.shape and g.dofs_shape == basis.dofs_shape):
+            return None
+        mode = 'iso'
+    elif isinstance(geom, function.RectilinearGeometry) and tuple(geom.topo.shape) == basis.shape:
+        mode = 'box' if os.environ.get('NUTILS_AMD_NO_UNIFORM') else 'uniform'
+    elif isinstance(geom, function.GradedGeometry) and tuple(geom.topo.shape) == basis.shape and geom.size.all():
+        mode = 'box'  # (axis-aligned cells, J = diag(size); flat cells: generic path, NaN rules of numeric.inv)
+    else:
+        return None
+    if (mode, nc) not in HEX1_ROUTED:
         return None
     return numpy.ascontiguousarray(C), geom, mode
 

@@ -333,3 +333,27 @@ def quad_form(shape, btype, degree, nc, uniform=False, seed=0):
     eps = lambda w: function.symgrad(w, geom)
     res = domain.integral(function.inner(eps(v), function.div(u, geom) * function.eye(2) + 1.3 * eps(u)) * dV, degree=2 * degree)
     return function.derivative(function.derivative(res, 'v'), 'u')
+
+
+def hex1_form(shape, kind='elasticity', uniform=False, degree=2, seed=0, graded=False):
+    '''The 3-D matrix integrals of tools/hex1_probe.py on the trilinear 'std' basis, Gauss degree `degree`: linear elasticity (lambda = 1, 2 mu = 1.3) or
+    anisotropic diffusion with a full constant tensor (kind='aniso'); geometry: the isoparametric P1 map of the unit grid with vertices perturbed by up to
+    0.2 (the mesh of tools/vector_probe.py), (uniform) the equidistant rectilinear cells, or (graded) cells graded quadratically towards one corner.  Returns
+    the terms of one matrix plan.'''
+    domain, geom = mesh.rectilinear([numpy.linspace(0, 1, n + 1) ** 2 for n in shape] if graded else list(shape))
+    if not uniform and not graded:
+        rng = numpy.random.default_rng(seed)
+        verts = numpy.stack(numpy.meshgrid(*[numpy.arange(n + 1.) for n in shape], indexing='ij'), -1).reshape(-1, 3)
+        geom = domain.basis('std', degree=1) @ (verts + rng.uniform(-.2, .2, verts.shape))
+    dV = function.J(geom)
+    if kind == 'aniso':
+        basis = domain.basis('std', degree=1)
+        (smp, itg, fac), = domain.integral(function.outer(function.grad(basis, geom)).sum(-1) * dV, degree=degree).terms
+        C = numpy.zeros((1, 4, 1, 4))
+        C[0, 1:, 0, 1:] = [[2., .3, .1], [.3, 1., -.2], [.1, -.2, 1.5]]
+        return [(smp, itg._copy(B=C), 1.)]
+    u = domain.field('u', btype='std', degree=1, shape=[3])
+    v = domain.field('v', btype='std', degree=1, shape=[3])
+    eps = lambda w: function.symgrad(w, geom)
+    res = domain.integral(function.inner(eps(v), function.div(u, geom) * function.eye(3) + 1.3 * eps(u)) * dV, degree=degree)
+    return function.derivative(function.derivative(res, 'v'), 'u').terms
