@@ -8,20 +8,25 @@ computed per element; `--variant uniform` times the exact-uniform mesh instead.
 `--config c3` (BASELINE.json configs[2]): 3-D linear elasticity, P2 vector basis, 64^3 elements, 3x3x3 Gauss.
 
 A "step" is one full (re)assembly of the CSR values with all inputs resident in HBM (vertex coordinates, tabulated
-bases, sparsity pattern): zero-fill (if the kernel accumulates) + element kernel; `value` is measured on that.  The
+bases, sparsity pattern): zero-fill (if the kernel accumulates) + element kernel; `value` is measured on that.  With `--full` the
 regions of BASELINE.md 3 are reported next to it: `first_assembly_ms` (pattern + values, device resident),
 `host_ready_ms` (pattern + values + the copy of (values, rowptr, colidx) to host memory, i.e. "CSR ready for scipy")
 and `reassembly_host_ready_ms` (values only); the CPU leg times pattern + values on the host, so
 `speedup_vs_cpu_port.first_assembly_host_ready` is the like-for-like ratio.
 
 With --gpus N (default `--scaling strong`, SURVEY.md 8e / BASELINE.json north_star: "elements are partitioned across the
-GPUs of one node"): the ONE n^3 mesh is split into N slabs of n/N element layers; the line also carries the weak-scaling
+GPUs of one node"): the ONE n^3 mesh is split into N slabs of n/N element layers; with `--full` the line also carries the weak-scaling
 figure of the same launch (`weak`: every rank assembles its own n^3-element slab of an (n N) x n x n mesh).  `--scaling weak`
 makes the weak figure the headline instead.  With the default `--halo recompute` no data moves between the ranks (each assembles its ghost element layer and
-writes the rows it owns); `--halo reduce` reduces the shared dof plane over RCCL (point to point, interface rows only).  At N = 1 the default line also carries `variants.c3` (BASELINE.json configs[2], measured in the
+writes the rows it owns); `--halo reduce` reduces the shared dof plane over RCCL (point to point, interface rows only).  At N = 1 the `--full` line also carries `variants.c3` (BASELINE.json configs[2], measured in the
 same run: kernel time by HIP events, HBM fraction, CPU port), `variants.c4` (configs[3]: one Newton step of the 512^2 Cahn-Hilliard system, tools/c4_step.py) and
 `variants.c5` (the configs[4] class: 63 488 ragged rational hierarchical elements, parity-checked against the reference fixture, tools/ragged_probe.py) and
 `variants.vector_any_mesh` (96^3 trilinear elasticity through the any-mesh entry: the owner kernel for vector-valued blocks, tools/vector_probe.py).
+
+A plain run does what the headline figure needs and nothing else: set-up, the untimed settle and warm-up steps, the timed steps, the gate on the assembled
+matrix (K 1 = 0 on the owned rows, read off the values of the last timed step), `--dump-outputs`, the line.  The timed steps are run three times, as ever:
+with HIP events around the kernel (`kernel_ms`), eager, then as a graph replay, which is the headline: what precedes the replay moves it (see timed_steps).  Everything
+else named above and below is measured with `--full` only: the roofline built on `kernel_ms`, the regions of BASELINE.md 3, the CPU leg, the traffic probe, every entry of `variants`, and with N > 1 the other scaling mode.
 
 Prints ONE JSON line on rank 0.
 '''
@@ -45,6 +50,10 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=None)
     ap.add_argument('--warmup', type=int, default=None)
+    ap.add_argument('--full', action='store_true',
+                    help='next to the headline figure, measure everything else the line can carry: the roofline, '
+                         'host-ready regions, CPU baseline, traffic probe, `variants`, the other scaling mode with N > 1.  Off by default: a plain run is set-up, warm-up, '
+                         'the timed steps and the gate on the assembled matrix')
     ap.add_argument('--config', choices=['c2', 'c3'], default='c2', help='c2: 128^3 P1 Poisson (headline); c3: 64^3 P2 vector elasticity')
     ap.add_argument('--scaling', choices=['weak', 'strong'], default=None, help='default: strong (one mesh split over the GPUs) when the element layers divide evenly, else weak')
     ap.add_argument('--halo', choices=['recompute', 'reduce'], default='recompute',
@@ -53,15 +62,15 @@ def parse():
     ap.add_argument('--compare-halo', action='store_true', help='N > 1: also time the other halo mode (secondary figure).  Off by default: the reduce mode is the only part of the '
                     'bench that moves data between ranks, and it has never run on multi-GPU hardware -- a stall there would take the headline line with it')
     ap.add_argument('--traffic', choices=['measure', 'static'], default='measure',
-                    help='roofline.traffic: measure = two rocprofv3 --pmc passes of a short probe of the same kernel inside this run (when rocprofv3 is on PATH), '
+                    help='--full: roofline.traffic: measure = two rocprofv3 --pmc passes of a short probe of the same kernel inside this run (when rocprofv3 is on PATH), '
                          'static = the committed profile file')
     ap.add_argument('--settle', type=int, default=None, help='untimed steps before the warm-up: the first ~50 launches after idle run ~10 %% slower (clock ramp)')
     ap.add_argument('--n', '--elements-per-axis', dest='n', type=int, default=None,
                     help='elements per axis (per GPU with weak scaling; use the long form behind torch.distributed.run, whose parser claims --n)')
     ap.add_argument('--variant', choices=['iso', 'uniform'], default='iso')
     ap.add_argument('--kernel', choices=['auto', 'generic', 'gather', 'fused', 'batched', 'fast'], default='auto')
-    ap.add_argument('--no-cpu', action='store_true', help='skip the cpu_baseline leg')
-    ap.add_argument('--no-c3', action='store_true', help='skip the configs[2] variant of the default line')
+    ap.add_argument('--no-cpu', action='store_true', help='--full: skip the cpu_baseline leg')
+    ap.add_argument('--no-c3', action='store_true', help='--full: skip the configs[2] variant of the line')
     ap.add_argument('--no-graph', dest='graph', action='store_false', help='launch every step eagerly instead of replaying a captured HIP graph')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last timed step computed (the CSR matrix K: a seeded sample of its entries) as DIR/<name>.npy')
@@ -180,7 +189,9 @@ def timed_steps(wl, steps, world, dist, use_graph):
 
     # Both launch modes are complete executions of exactly `steps` steps and both are reported (`ms_per_step_eager`, `ms_per_step_graph`);
     # the headline is the graph replay whenever the step can be captured -- that is how a time loop would issue a launch-bound step -- and
-    # is NOT chosen after the fact.
+    # is NOT chosen after the fact.  The pass with HIP events and the eager run belong to the protocol of the headline, in a plain run as well:
+    # what is launched before the timed replay moves it (128^3, 200 steps, four runs each: 0.1675-0.1689 ms right after the eager run, 0.1709-0.1739 ms
+    # right after the warm-up).
     eager = run(False)
     modes = {'ms_per_step_eager': eager / steps * 1e3}
     elapsed, launch = eager, 'eager'
@@ -391,6 +402,42 @@ def c3_roofline(wl, kernel_ms, traffic):
                      'matrix_pipe_busy': wl.mfma_per_element() * wl.nelems * 64 / 1024 / (kernel_ms * 1e-3 * 2.4e9)}}
 
 
+def headline_roofline(a, wl, kernel_ms, wl_nelems, wl_layers, world):
+    """--full: the kernel of the headline against the HBM peak (algorithmic bytes over the duration between HIP events), with the HBM traffic of a launch from
+    the in-run probe or the committed profile file."""
+    bytes_per_elem = wl.algorithmic_bytes_per_element()
+    gbs = bytes_per_elem * wl_nelems / (kernel_ms * 1e-3) / 1e9
+    traffic = measured_traffic(wl.kernel_name, a.n) if world == 1 else None
+    inrun = None
+    if world == 1 and a.traffic == 'measure':
+        probe = [sys.executable, 'tools/c3_bench.py', str(a.n), '3'] if a.config == 'c3' else [sys.executable, 'tools/c2_time.py', str(a.n), '30']
+        if a.config == 'c3' or (a.variant == 'iso' and a.kernel in ('auto', 'fast')):
+            inrun = measured_traffic_inrun(wl.kernel_name.split('<')[0], probe)
+        if inrun is not None:
+            traffic = inrun['bytes']
+    if a.config == 'c3':
+        roofline = c3_roofline(wl, kernel_ms, traffic)
+    else:
+        roofline = {'bound': 'hbm', 'achieved': gbs, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': gbs / HBM_PEAK_GBS, 'traffic': traffic,
+                    'kernel': wl.kernel_name, 'kernel_ms': kernel_ms, 'algorithmic_bytes_per_element': bytes_per_elem}
+        if a.variant == 'iso' and a.kernel in ('auto', 'fast'):
+            # second roofline of the same kernel: EXECUTED f64 arithmetic against the f64 vector peak.  Per element-thread the routine issues 1060 f64
+            # instructions = 1489 flop (ISA of nh_p1hex_math.inc + the 36 entries: 301 mul, 330 add, 429 fma; tools/isa_hist.sh) plus 8 reciprocals; the
+            # kernel computes every element of its 16 x 16 tiles incl. the one-element lateral halo and one extra layer per run of a workgroup.
+            nb = -(-(a.n + 1) // 15)
+            threads = nb * nb * 256 * (wl_layers + max(1, round(256 / (nb * nb))))
+            tf = 1489. * threads / (kernel_ms * 1e-3) / 1e12
+            roofline['f64_valu'] = {'achieved': tf, 'peak': F64_MFMA_PEAK_TF, 'unit': 'TFLOP/s', 'frac': tf / F64_MFMA_PEAK_TF, 'flop_per_element_thread': 1489,
+                                    'f64_instructions_per_element_thread': 1060, 'element_threads': threads,
+                                    'note': 'executed arithmetic incl. halo recompute (1.27 x the elements); counters: profiles/r04_c2_kernels.md section 2'}
+    if inrun is not None:
+        roofline['traffic_source'] = inrun['source']
+        roofline['traffic_detail'] = {k: inrun[k] for k in ('fetch_bytes', 'write_bytes', 'bytes_fetch_doubled')}
+    elif traffic is not None:
+        roofline['traffic_source'] = TRAFFIC_FILE + ' (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE of this command, separate passes; not measured in this run)'
+    return roofline
+
+
 def main():
     a = parse()
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')  # dmabuf IPC: required by RCCL / cross-process device memory on this driver
@@ -454,12 +501,12 @@ def main():
                       'checks': ch, **getattr(timed_steps, 'last_modes', {})}
         del wh
         torch.cuda.empty_cache()
-    if world > 1:
+    wl_nelems, wl_layers, nnz = wl.nelems, wl.layers, wl.nnz  # (sizes of the primary run)
+    if world > 1 and a.full:
         # the other scaling mode of the same launch (secondary figure; fewer settle steps -- the clocks are up)
         mode2 = 'weak' if strong else 'strong'
         n = a.n
         if not (mode2 == 'strong' and n % world):
-            nelems1, layers1, nnz1 = wl.nelems, wl.layers, wl.nnz
             del wl
             torch.cuda.empty_cache()
             w2 = make_workload(a, a.config, mode2, rank, world)()
@@ -473,48 +520,15 @@ def main():
             other = {'scaling': mode2, 'value': w2.nelems * world * a.steps / el2, 'unit': 'elements/s', 'ms_per_step': el2 / a.steps * 1e3, 'kernel_ms': kms2,
                      'nelems_per_gpu': w2.nelems, 'checks': c2}
             wl = w2  # (only sizes of the primary run are reported below)
-            wl_nelems, wl_layers, nnz = nelems1, layers1, nnz1
-        else:
-            wl_nelems, wl_layers, nnz = wl.nelems, wl.layers, wl.nnz
-    else:
-        wl_nelems, wl_layers, nnz = wl.nelems, wl.layers, wl.nnz
 
     if rank == 0:
         nelems_total = wl_nelems * world
         value = nelems_total * a.steps / elapsed
-        bytes_per_elem = wl.algorithmic_bytes_per_element()
-        gbs = bytes_per_elem * wl_nelems / (kernel_ms * 1e-3) / 1e9
-        traffic = measured_traffic(wl.kernel_name, a.n) if world == 1 else None
-        inrun = None
-        if world == 1 and a.traffic == 'measure':
-            probe = [sys.executable, 'tools/c3_bench.py', str(a.n), '3'] if a.config == 'c3' else [sys.executable, 'tools/c2_time.py', str(a.n), '30']
-            if a.config == 'c3' or (a.variant == 'iso' and a.kernel in ('auto', 'fast')):
-                inrun = measured_traffic_inrun(wl.kernel_name.split('<')[0], probe)
-            if inrun is not None:
-                traffic = inrun['bytes']
         if a.config == 'c3':
-            roofline = c3_roofline(wl, kernel_ms, traffic)
             workload = f'3D linear elasticity stiffness, {a.n}^3 structured hex, p=2 vector basis (81 local dofs), 3x3x3 Gauss, {a.variant} geometry (BASELINE.json configs[2])'
         else:
-            roofline = {'bound': 'hbm', 'achieved': gbs, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s', 'frac': gbs / HBM_PEAK_GBS, 'traffic': traffic,
-                        'kernel': wl.kernel_name, 'kernel_ms': kernel_ms, 'algorithmic_bytes_per_element': bytes_per_elem}
-            if a.variant == 'iso' and a.kernel in ('auto', 'fast'):
-                # second roofline of the same kernel: EXECUTED f64 arithmetic against the f64 vector peak.  Per element-thread the routine issues 1060 f64
-                # instructions = 1489 flop (ISA of nh_p1hex_math.inc + the 36 entries: 301 mul, 330 add, 429 fma; tools/isa_hist.sh) plus 8 reciprocals; the
-                # kernel computes every element of its 16 x 16 tiles incl. the one-element lateral halo and one extra layer per run of a workgroup.
-                nb = -(-(a.n + 1) // 15)
-                threads = nb * nb * 256 * (wl_layers + max(1, round(256 / (nb * nb))))
-                tf = 1489. * threads / (kernel_ms * 1e-3) / 1e12
-                roofline['f64_valu'] = {'achieved': tf, 'peak': F64_MFMA_PEAK_TF, 'unit': 'TFLOP/s', 'frac': tf / F64_MFMA_PEAK_TF, 'flop_per_element_thread': 1489,
-                                        'f64_instructions_per_element_thread': 1060, 'element_threads': threads,
-                                        'note': 'executed arithmetic incl. halo recompute (1.27 x the elements); counters: profiles/r04_c2_kernels.md section 2'}
             per = f'{wl_layers} x {a.n} x {a.n} per GPU' if world > 1 else f'{a.n}^3'
             workload = f'3D Poisson stiffness, {per} structured hex, p=1, 2x2x2 Gauss, {a.variant} geometry (BASELINE.json configs[1])'
-        if inrun is not None:
-            roofline['traffic_source'] = inrun['source']
-            roofline['traffic_detail'] = {k: inrun[k] for k in ('fetch_bytes', 'write_bytes', 'bytes_fetch_doubled')}
-        elif traffic is not None:
-            roofline['traffic_source'] = TRAFFIC_FILE + ' (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE of this command, separate passes; not measured in this run)'
         out = {
             'metric': metric, 'value': value, 'unit': 'elements/s', 'n_gpus': world,
             'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': elapsed / a.steps * 1e3, 'higher_is_better': True, 'scaling': a.scaling,  # (one GPU: both modes coincide; the series N = 1, 2, 4, 8 carries one label)
@@ -523,18 +537,20 @@ def main():
                        'parallelism': (f'element slabs x{world}, ' + ('one ghost element layer recomputed per rank, no exchange' if a.halo == 'recompute' else 'halo-plane reduce (RCCL point to point)'))
                        if world > 1 else 'single GPU', 'halo': a.halo if world > 1 else None, 'launch': launch,
                        'settle_steps': settled, 'timed_region': 'device-resident re-assembly of the CSR values (pattern, tables, vertices in HBM)'},
-            'roofline': roofline, 'pattern_ms': pattern_ms, 'setup_s': setup_s, 'checks': checks,
+            'kernel_ms': kernel_ms, 'pattern_ms': pattern_ms, 'setup_s': setup_s, 'checks': checks,
         }
         out.update(launch_modes)
+        if a.full:
+            out['roofline'] = headline_roofline(a, wl, kernel_ms, wl_nelems, wl_layers, world)
         if other is not None:
             out[other['scaling']] = other
         if other_halo is not None:
             out['halo_' + other_halo['halo']] = other_halo
-        if world == 1:
+        if a.full and world == 1:
             del wl
             torch.cuda.empty_cache()
             out.update(host_regions(lambda: make(0, 1), copy=a.config == 'c2'))
-        if world == 1 and a.variant == 'iso' and a.config == 'c2':
+        if a.full and world == 1 and a.variant == 'iso' and a.config == 'c2':
             # secondary variant of the same config: exact-uniform mesh (what mesh.rectilinear gives the reference; there the
             # element matrix is hoisted out of the loop and the work is index generation + dedup).  Not the headline value.
             w2 = workloads.PoissonSlab(n=a.n, rank=0, world=1, variant='uniform', kernel=a.kernel)
@@ -634,7 +650,7 @@ def main():
                             out['variants'][key]['traffic'] = measured_traffic('c5 step: k_gram_sym (both size classes) + k_gather_values_2x2_tri + k_mirror_2x2', 256)
                     except Exception as e:  # noqa: BLE001 (secondary figures)
                         out['variants'][key] = {'error': f'{type(e).__name__}: {e}'[:200]}
-        if not a.no_cpu and world == 1:
+        if a.full and not a.no_cpu and world == 1:
             cb = cpu_baseline_c3(make(0, 1)) if a.config == 'c3' else cpu_baseline_c2(a.variant)
             if cb:
                 out['cpu_baseline'] = cb

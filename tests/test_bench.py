@@ -1,4 +1,4 @@
-'''bench.py --dump-outputs: what the timed step computed, written for comparison between builds.'''
+'''bench.py: --dump-outputs (what the timed step computed, written for comparison between builds) and --full (the secondary figures).'''
 import json
 import os
 import subprocess
@@ -76,3 +76,20 @@ def test_bench_dumps_the_timed_matrix(tmp_path):
     assert numpy.array_equal(d['rows'], numpy.repeat(numpy.arange(len(rp) - 1), numpy.diff(rp))) and numpy.array_equal(d['cols'], ci)
     assert numpy.abs(d['values'] - v).max() <= 1e-13 * numpy.abs(v).max()
     assert d['summary'][:2].tolist() == [len(rp) - 1, len(v)]
+
+
+@pytest.mark.gpu
+def test_full_option_carries_the_secondary_figures():
+    '''A plain run prints the headline figure and its gate only; `--full` prints the same line with the figures that take runs of their own.'''
+    secondary = ('roofline', 'first_assembly_ms', 'host_ready_ms', 'reassembly_host_ready_ms', 'variants')
+    recs = {}
+    for full in ([], ['--full', '--no-cpu', '--traffic', 'static']):  # (the plain leg without the options that switch secondary figures off)
+        cmd = [sys.executable, 'bench.py', '--steps', '3', '--warmup', '1', '--settle', '0', '--elements-per-axis', '8'] + full
+        out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        rec = recs[bool(full)] = json.loads([l for l in out.stdout.splitlines() if l.startswith('{"metric"')][0])
+        assert rec['steps'] == 3 and rec['value'] > 0 and rec['unit'] == 'elements/s' and rec['higher_is_better'] is True and rec['dtype'] == 'f64'
+        assert abs(rec['value'] * rec['ms_per_step'] * 1e-3 / 8 ** 3 - 1) < 1e-9 and rec['checks']['owned_row_sums_rel'] < 1e-12 and rec['kernel_ms'] > 0
+    assert not [k for k in secondary + ('cpu_baseline', 'speedup_vs_cpu_port') if k in recs[False]]
+    assert not [k for k in secondary if k not in recs[True]]
+    assert recs[True]['roofline']['kernel_ms'] > 0 and set(recs[True]['variants']) == {'uniform', 'generic_gather', 'generic_fused'}

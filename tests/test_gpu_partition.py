@@ -133,14 +133,14 @@ def test_pipelined_exchange_matches_serial():
 
 @pytest.mark.parametrize('world', [2, 3, 4])  # (4: two interior ranks; with the test process five processes hold the GPU -- keep that at six or fewer)
 def test_bench_multiprocess_on_one_gpu(world):
-    '''`bench.py --gpus N` exactly as the driver launches it (torch.distributed.run, one process per rank), except that all ranks
+    '''`bench.py --gpus N --full` as a multi-GPU launch runs it (torch.distributed.run, one process per rank), except that all ranks
     share the one GPU of this box and the interface rows travel through gloo (host staging) instead of RCCL: exercises rank
     bookkeeping, ghost layers, the pipelined exchange, the timing protocol and the owned-row-sum check of every rank.'''
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, NUTILS_AMD_BENCH_ONE_GPU='1', MASTER_ADDR='127.0.0.1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', f'--nproc-per-node={world}', '--master-addr', '127.0.0.1', '--master-port', str(29500 + world),
-           'bench.py', '--gpus', str(world), '--steps', '4', '--warmup', '2', '--elements-per-axis', '32', '--no-cpu', '--compare-halo']
+           'bench.py', '--gpus', str(world), '--steps', '4', '--warmup', '2', '--elements-per-axis', '32', '--full', '--no-cpu', '--compare-halo']
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{"metric"')]
@@ -160,6 +160,26 @@ def test_bench_multiprocess_on_one_gpu(world):
     assert 'WARNING' not in out.stderr
 
 
+def test_bench_plain_multiprocess_on_one_gpu():
+    '''`bench.py --gpus 2` without --full, two ranks on one GPU: the line of the strong split with its gate and the sizes of that run, and no other scaling mode;
+    --compare-halo is an option of its own and still carries the reduce figure.'''
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, NUTILS_AMD_BENCH_ONE_GPU='1', MASTER_ADDR='127.0.0.1')
+    cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node=2', '--master-addr', '127.0.0.1', '--master-port', '29512',
+           'bench.py', '--gpus', '2', '--steps', '4', '--warmup', '2', '--settle', '2', '--elements-per-axis', '32', '--compare-halo']
+    out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith('{"metric"')]
+    assert len(lines) == 1, out.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec['n_gpus'] == 2 and rec['steps'] == 4 and rec['scaling'] == 'strong' and rec['value'] > 0
+    assert rec['config']['nelems_per_gpu'] == 32 ** 3 // 2 and rec['config']['nnz_per_gpu'] > 0 and '16 x 32 x 32 per GPU' in rec['config']['workload']
+    assert abs(rec['value'] * rec['ms_per_step'] * 1e-3 / 32 ** 3 - 1) < 1e-9
+    assert rec['checks']['owned_row_sums_rel'] < 1e-12 and rec['halo_reduce']['value'] > 0
+    assert not [k for k in ('weak', 'strong', 'roofline', 'variants', 'cpu_baseline', 'first_assembly_ms') if k in rec]
+
+
 @pytest.mark.parametrize('args,nel', [(['--scaling', 'weak', '--elements-per-axis', '32'], 32 ** 3),
                                       (['--config', 'c3', '--scaling', 'weak', '--elements-per-axis', '8'], 8 ** 3),
                                       (['--config', 'c3', '--elements-per-axis', '8'], 8 ** 3 // 2)])
@@ -169,7 +189,7 @@ def test_bench_modes_multiprocess_on_one_gpu(args, nel):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, NUTILS_AMD_BENCH_ONE_GPU='1', MASTER_ADDR='127.0.0.1')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node=2', '--master-addr', '127.0.0.1', '--master-port', '29511',
-           'bench.py', '--gpus', '2', '--steps', '3', '--warmup', '1', '--settle', '2', '--no-cpu'] + args
+           'bench.py', '--gpus', '2', '--steps', '3', '--warmup', '1', '--settle', '2', '--full', '--no-cpu'] + args
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith('{"metric"')][0])

@@ -2,9 +2,10 @@
 # round-5 evidence run (GPU box, from the repo root): the bench line, its kernel trace, kernel traces and HBM traffic (PMC, separate passes) of the owner kernels
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
-python bench.py > gpurun_out/r5_bench.json 2> gpurun_out/r5_bench.err
-tail -c 600 gpurun_out/r5_bench.json
-KT_LINES=16 KT_TAIL=1 bash tools/kt.sh r5_bench python bench.py --no-cpu --traffic static > /dev/null
+out=${BENCH_OUT:-bench_out}; mkdir -p $out
+python bench.py --full > $out/r5_bench.json 2> $out/r5_bench.err
+tail -c 600 $out/r5_bench.json
+KT_LINES=16 KT_TAIL=1 bash tools/kt.sh r5_bench python bench.py --full --no-cpu --traffic static > /dev/null
 KT_LINES=10 KT_TAIL=2 bash tools/kt.sh r5_vector python tools/vector_probe.py 96 10 > /dev/null
 NUTILS_AMD_NO_FAST_PATH=1 KT_LINES=8 KT_TAIL=1 bash tools/kt.sh r5_generic python tools/generic_probe.py "3D P1 128" > /dev/null
 for c in FETCH_SIZE WRITE_SIZE; do

@@ -1,11 +1,12 @@
 #!/bin/bash
 # evidence of the round's state (GPU box, from the repo root): the default bench line, the kernel trace of the same command, PMC traffic (separate passes) of kernels the
-# static traffic file lacks -> gpurun_out/r6f_*
+# static traffic file lacks; the bench line goes to $BENCH_OUT, the traces and counters where tools/kt.sh and tools/pmc.sh put them
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
-python bench.py > gpurun_out/r6f_bench.json 2> gpurun_out/r6f_bench.err
-tail -c 300 gpurun_out/r6f_bench.json
-KT_LINES=26 KT_TAIL=1 bash tools/kt.sh r6f_bench python bench.py --no-cpu --traffic static > /dev/null
+out=${BENCH_OUT:-bench_out}; mkdir -p $out
+python bench.py --full > $out/r6f_bench.json 2> $out/r6f_bench.err
+tail -c 300 $out/r6f_bench.json
+KT_LINES=26 KT_TAIL=1 bash tools/kt.sh r6f_bench python bench.py --full --no-cpu --traffic static > /dev/null
 cat gpurun_out/kt_r6f_bench.txt | cut -c1-200 | head -8
 for c in FETCH_SIZE WRITE_SIZE; do
   echo "== c3 uniform $c" | tee -a gpurun_out/r6f_traffic.txt
