@@ -669,6 +669,47 @@ int nh_point_expr(int64_t npoints, int nvars, const double *const *x_dev, const 
 int nh_rationalize(double *T_dev, int64_t nelems, int nb, const int64_t *off_dev, const int32_t *dofs_dev, const double *weights_dev,
                    const double *W_dev, const double *dW_dev, int nq, int ndims, void *stream);
 
+/* ---- device-resident matrix: CSR product, diagonal, conjugate gradients ------------------------------
+ * The matrix backend that fits the data of this library (the slot matrix/_mkl.py fills for the vendor library of the host): the
+ * CSR triplet stays where the assembly left it, is multiplied there (Matrix.__matmul__, matrix/_base.py) and symmetric positive
+ * definite systems are solved there (Matrix.solve with solver='cg'; constraints as a row mask instead of a submatrix).
+ * nh_csr is a plain view: sizes and device pointers, nothing owned.  values f64, rowptr int64 [nrows + 1].  Column indices: col32_dev
+ * (int32 [nnz], made once per matrix by nh_csr_compact; needs ncols <= INT32_MAX) if not NULL, else colidx_dev (the int64 [nnz] of the
+ * assembly) -- 12 against 16 bytes per entry.  lanes: lanes of a wave that share a row, a power of two 1 .. 64; 0 = nh_csr_lanes(nrows,
+ * nnz), two thirds of the mean row length rounded down to a power of two, at most 32.
+ * Argument errors (NULL pointers, negative sizes, a bad `lanes`, int32 columns with ncols > INT32_MAX) return NH_EINVAL before
+ * anything touches the device.  nrows == 0 succeeds without a launch; so does nnz == 0 where the result is known without one. */
+typedef struct {
+  int64_t nrows, ncols, nnz;
+  const double *values_dev;
+  const int64_t *rowptr_dev;
+  const int64_t *colidx_dev;
+  const int32_t *col32_dev;
+  int lanes;
+} nh_csr;
+
+int nh_csr_lanes(int64_t nrows, int64_t nnz);  /* the rule behind lanes = 0 (host computation, returns the lane count) */
+int nh_csr_compact(int64_t nnz, int64_t ncols, const int64_t *colidx_dev, int32_t *col32_dev, void *stream);
+/* y = mask(alpha A x + beta b): rowmask_dev uint8 [nrows] or NULL, rows with mask 0 get y = 0 (their entries are not read); b_dev may be
+ * NULL (no second term) and may be y_dev; x_dev must not overlap y_dev.  No atomics, and the launch geometry depends on (nrows, lanes)
+ * only: repeated calls are bit-identical. */
+int nh_csr_spmv(const nh_csr *A, double alpha, const double *x_dev, double beta, const double *b_dev, const unsigned char *rowmask_dev, double *y_dev, void *stream);
+/* diag[i] = A_ii, 0 for a row without a diagonal entry (Matrix.diagonal) */
+int nh_csr_diagonal(const nh_csr *A, double *diag_dev, void *stream);
+/* Preconditioned conjugate gradients for square A, symmetric positive definite on the rows / columns the mask keeps, entirely on the
+ * device: an iteration is three launches -- q = mask(A p) with partial sums of p . q per workgroup; alpha from the partials (summed by
+ * every workgroup in the same order), x += alpha p, r -= alpha q, partials of r . z and r . r with z = dinv r; beta from those and
+ * p = z + beta p -- and nothing is read back.  work_dev: nh_cg_work_doubles() doubles; after every iteration work[0] = r . r of the
+ * recurrence and work[1] = the breakdown flag (0. / 1.): one 16-byte copy tells the host where the iteration stands.  The flag is raised
+ * when r != 0 and p . q or r . z is not a positive finite number (A or the preconditioner is not positive definite); from then on the
+ * iterations leave x, r and p as they are.  dinv_dev: inverse diagonal (Jacobi) or NULL (none); it must be finite, and r and p zero, on
+ * masked rows.  nh_cg_init forms p = z = dinv r and the first r . z, r . r from a given r and clears the flag; nh_cg_iterate enqueues
+ * niter iterations. */
+int64_t nh_cg_work_doubles(void);
+int nh_cg_init(int64_t n, const double *dinv_dev, const double *r_dev, double *p_dev, double *work_dev, void *stream);
+int nh_cg_iterate(const nh_csr *A, const unsigned char *rowmask_dev, const double *dinv_dev, double *x_dev, double *r_dev, double *p_dev, double *q_dev,
+                  double *work_dev, int niter, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

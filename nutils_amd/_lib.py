@@ -122,6 +122,11 @@ class Hex1Args(ctypes.Structure):
                 ('C_host', vp), ('values_dev', vp)]
 
 
+class Csr(ctypes.Structure):
+    _fields_ = [('nrows', c_i64), ('ncols', c_i64), ('nnz', c_i64), ('values_dev', vp), ('rowptr_dev', vp), ('colidx_dev', vp), ('col32_dev', vp),
+                ('lanes', ctypes.c_int)]
+
+
 GEOM_ISO = 1
 GEOM_BOX = 2
 GEOM_TAB = 3
@@ -189,6 +194,13 @@ SIGNATURES = {
     'nh_hex1_pattern': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.c_int, vp, vp, vp]),
     'nh_hex1_matrix': (ctypes.c_int, [ctypes.POINTER(Hex1Args), vp]),
     'nh_hex1_rows_uniform': (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.c_int, vp, vp, vp]),
+    'nh_csr_lanes': (ctypes.c_int, [c_i64, c_i64]),
+    'nh_csr_compact': (ctypes.c_int, [c_i64, c_i64, vp, vp, vp]),
+    'nh_csr_spmv': (ctypes.c_int, [ctypes.POINTER(Csr), ctypes.c_double, vp, ctypes.c_double, vp, vp, vp, vp]),
+    'nh_csr_diagonal': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp]),
+    'nh_cg_work_doubles': (c_i64, []),
+    'nh_cg_init': (ctypes.c_int, [c_i64, vp, vp, vp, vp, vp]),
+    'nh_cg_iterate': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, vp, vp, vp, vp, vp, ctypes.c_int, vp]),
 }
 
 _lib = None

@@ -144,13 +144,21 @@ class FactoredMatrix:
     def __init__(self, parent):
         self.parent = parent
 
-    def as_csr(self):
+    def _triplet(self):
         if self.parent.T:
             raise NotImplementedError('Hessian of a factored functional of degree >= 3 (depends on the argument): integrate the second derivative instead')
         if len(self.parent.K) != 1:
             raise NotImplementedError('sum of tensors with different patterns: assemble per sample and add')
-        values, rowptr, colidx = self.parent.K[0]
+        return self.parent.K[0]
+
+    def as_csr(self):
+        values, rowptr, colidx = self._triplet()
         return device.to_host(values), device.to_host(rowptr), device.to_host(colidx)
+
+    def as_matrix(self):
+        '''the device tensors themselves as a matrix.HipMatrix (which does not write into them)'''
+        from . import matrix
+        return matrix.HipMatrix(*self._triplet(), self.parent.size)
 
 
 def factor(integral, name=None):

@@ -922,6 +922,19 @@ class _AsCOO:
         self.integral = integral
 
 
+class _AsMatrix(_AsCSR):
+    pass
+
+
+def as_matrix(integral):
+    '''Sibling of `as_csr` for the device-resident backend: evaluates to a `matrix.HipMatrix` on the CSR triplet the assembly left in HBM -- values and
+    indices are not copied to the host.'''
+    from . import factor as _factor
+    if not isinstance(integral, (Integral, _factor.FactoredMatrix)):
+        raise TypeError('as_matrix expects an Integral')
+    return _AsMatrix(integral)
+
+
 def as_coo(integral):
     '''function.as_coo (function.py:2440-2452): (values, rowidx, colidx).'''
     return _AsCOO(integral)

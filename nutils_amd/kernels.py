@@ -811,3 +811,54 @@ class Hex1Uniform:
         if _lib.TRACE is not None:
             _lib.TRACE.append(self._name)
         _lib.check(self._fn(self._shape, self._nc, self.table.data_ptr(), values.data_ptr(), device.stream()))
+
+
+# ---- device-resident CSR matrix (nh_csr.hip) ---------------------------------------------------------
+
+def _csr(values, rowptr, colidx, ncols, col32, lanes):
+    return _lib.Csr(rowptr.numel() - 1, int(ncols), values.numel(), device.ptr(values), device.ptr(rowptr), device.ptr(colidx), device.ptr(col32), int(lanes))
+
+
+def csr_lanes(nrows, nnz):
+    '''lanes per row the library takes for `lanes=0` (nh_csr_lanes; a host computation)'''
+    return _lib.load().nh_csr_lanes(int(nrows), int(nnz))
+
+
+def csr_compact(colidx, ncols):
+    '''int32 copy of the int64 column indices (nh_csr_compact)'''
+    col32 = device.empty(colidx.numel(), 'int32')
+    _lib.call('nh_csr_compact', colidx.numel(), int(ncols), device.ptr(colidx), device.ptr(col32), device.stream())
+    return col32
+
+
+def csr_spmv(values, rowptr, colidx, ncols, x, *, y=None, alpha=1., beta=0., b=None, rowmask=None, col32=None, lanes=0):
+    '''y = mask(alpha A x + beta b) (nh_csr_spmv).  col32: the narrowed column indices of `csr_compact`; None: the kernel reads the int64 `colidx`.
+    lanes: lanes per row (0: the library's rule).  `b` may be `y`.'''
+    if y is None:
+        y = device.empty(rowptr.numel() - 1, 'float64')
+    _lib.call('nh_csr_spmv', ctypes.byref(_csr(values, rowptr, colidx, ncols, col32, lanes)), float(alpha), device.ptr(x), float(beta), device.ptr(b),
+              device.ptr(rowmask), device.ptr(y), device.stream())
+    return y
+
+
+def csr_diagonal(values, rowptr, colidx, ncols, *, col32=None):
+    '''diag[i] = A_ii or 0 (nh_csr_diagonal)'''
+    diag = device.empty(rowptr.numel() - 1, 'float64')
+    _lib.call('nh_csr_diagonal', ctypes.byref(_csr(values, rowptr, colidx, ncols, col32, 0)), device.ptr(diag), device.stream())
+    return diag
+
+
+def cg_work():
+    '''the work array of a CG solve (nh_cg_work_doubles): [0] = r . r of the recurrence, [1] = breakdown flag'''
+    return device.empty(_lib.load().nh_cg_work_doubles(), 'float64')
+
+
+def cg_init(dinv, r, p, work):
+    '''p = z = dinv r, first r . z and r . r, flag cleared (nh_cg_init)'''
+    _lib.call('nh_cg_init', r.numel(), device.ptr(dinv), device.ptr(r), device.ptr(p), device.ptr(work), device.stream())
+
+
+def cg_iterate(values, rowptr, colidx, ncols, *, rowmask, dinv, x, r, p, q, work, niter, col32=None, lanes=0):
+    '''enqueue `niter` CG iterations (nh_cg_iterate): three launches each, nothing read back'''
+    _lib.call('nh_cg_iterate', ctypes.byref(_csr(values, rowptr, colidx, ncols, col32, lanes)), device.ptr(rowmask), device.ptr(dinv), device.ptr(x), device.ptr(r),
+              device.ptr(p), device.ptr(q), device.ptr(work), int(niter), device.stream())

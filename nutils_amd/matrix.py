@@ -4,7 +4,16 @@ back to the host solver exactly the way the reference's evaluator hands it over
 rowptr, colidx, ncols)`` validates the triplet and calls
 ``backend.current.assemble``.  The validation is vectorised here (the reference
 uses Python ``all()`` over numpy arrays); the error behaviour (MatrixError, same
-conditions) is the reference's.  Solvers stay on the host (scipy), out of scope.
+conditions) is the reference's.
+
+Two backends.  'scipy' (the default; 'auto' means the same) wraps the host copy
+of the triplet in a ``ScipyMatrix`` with a direct solver.  'hip' keeps the
+triplet in HBM as a ``HipMatrix``: products, the diagonal and a Jacobi-
+preconditioned conjugate-gradient solve for symmetric positive definite systems
+run on the device (nh_csr.hip); ``function.eval(function.as_matrix(K))`` builds
+one without the triplet ever visiting the host.  What a ``HipMatrix`` does
+through scipy and a re-upload -- ``submatrix``, ``T``, every solver other than
+'cg', sums of matrices with different patterns -- says so in its docstring.
 '''
 
 import contextlib
@@ -13,6 +22,15 @@ import numpy
 
 class MatrixError(Exception):
     '''General error message for matrix-related failure (matrix/_base.py:9-12).'''
+
+
+class ToleranceNotReached(MatrixError):
+    '''The iterative solver stopped above the requested tolerance (matrix/_base.py:22-30); ``.best`` is the vector it had reached,
+    constrained values included.'''
+
+    def __init__(self, best):
+        super().__init__('solver failed to reach tolerance')
+        self.best = best
 
 
 class ScipyMatrix:
@@ -87,6 +105,317 @@ class _ScipyBackend:
         return ScipyMatrix(core)
 
 
+def spmv_lanes(nrows, nnz):
+    '''Lanes of a wave that share a row in the device product: two thirds of the mean row length rounded down to a power of two, between 1 and 32
+    (the rule of nh_csr_lanes; profiles/matrix_backend.md has the sweep it comes from: 4 lanes were fastest for 9 entries per row, 16 for 27, 32 for 81 and
+    for P2 vector rows of 185 on average).  The kernel itself takes any power of two up to 64.  Rows shorter than the lane count leave lanes idle, longer ones
+    are walked in strides.'''
+    nrows, nnz = int(nrows), int(nnz)
+    if nrows <= 0 or nnz <= 0:
+        return 1
+    target = 2 * nnz // (3 * nrows)
+    lanes = 1
+    while lanes < 32 and 2 * lanes <= target:
+        lanes *= 2
+    return lanes
+
+
+def constraints(ncols, constrain=None, lhs0=None):
+    '''(free, lhs) of a constrained solve in the reference's convention (matrix/_base.py:100-176): `constrain` is None (all dofs free), a float array
+    in which NaN marks a free dof and a number the value the dof is held at, or a bool array in which True holds the dof at its value in `lhs0`
+    (zero without one).  `free` is a bool vector, `lhs` a fresh float vector: `lhs0` with the constrained values written in.'''
+    ncols = int(ncols)
+    if lhs0 is None:
+        lhs = numpy.zeros(ncols)
+    else:
+        lhs = numpy.array(lhs0, dtype=float)
+        if lhs.shape != (ncols,):
+            raise MatrixError(f'initial vector has shape {lhs.shape}, expected ({ncols},)')
+    if constrain is None:
+        return numpy.ones(ncols, dtype=bool), lhs
+    constrain = numpy.asarray(constrain)
+    if constrain.shape != (ncols,):
+        raise MatrixError(f'constraints have shape {constrain.shape}, expected ({ncols},)')
+    if constrain.dtype == bool:
+        return ~constrain, lhs
+    if constrain.dtype.kind not in 'fiu':
+        raise MatrixError(f'constraints must be a float or bool array, got {constrain.dtype}')
+    constrain = constrain.astype(float)
+    free = numpy.isnan(constrain)
+    lhs[~free] = constrain[~free]
+    return free, lhs
+
+
+def _is_tensor(a):
+    return type(a).__module__.split('.')[0] == 'torch'
+
+
+def _host(a):
+    if a is None or not _is_tensor(a):
+        return a
+    from . import device
+    return device.to_host(a)
+
+
+class HipMatrix:
+    '''CSR matrix that lives in HBM, with the interface of the reference's Matrix (matrix/_base.py): `shape`, `size`, `@`, `diagonal`, `export`, scalar
+    multiples, sums, `submatrix`, `T`, `solve`, `solve_leniently`.
+
+    `values` (f64), `rowptr`, `colidx` (int64) are device tensors as `_MatrixPlan.run` returns them, or host arrays, which are validated and uploaded at the
+    first use on the device.  The matrix keeps references and never writes into them.  At the first product the column indices are narrowed to int32 once
+    (12 instead of 16 bytes per entry; matrices with more than 2^31 - 1 columns keep the int64 indices).
+
+    On the device: products (nh_csr_spmv), the diagonal, scalar multiples, sums of matrices that share their index tensors, and `solve(solver='cg')`, a
+    Jacobi-preconditioned conjugate-gradient iteration for SYMMETRIC POSITIVE DEFINITE systems with ONE right-hand side.  Through scipy and PCIe (export, host
+    operation, re-upload): `submatrix`, `T`, sums of matrices with different patterns, every other solver.'''
+
+    def __init__(self, values, rowptr, colidx, ncols, *, validate=True):
+        self._ncols = int(ncols)
+        if _is_tensor(values):
+            self._dev = (values, rowptr, colidx)
+            self._hostcsr = None
+            nrows, nnz = rowptr.numel() - 1, values.numel()
+        else:
+            values, rowptr, colidx = numpy.asarray(values, dtype=float), numpy.asarray(rowptr), numpy.asarray(colidx)
+            if validate:  # (the product trusts the column indices)
+                _check_triplet(values, rowptr, colidx, self._ncols)
+            self._dev = None
+            self._hostcsr = (values, rowptr, colidx)
+            nrows, nnz = len(rowptr) - 1, len(values)
+        self.shape = (nrows, self._ncols)
+        self.nnz = nnz
+        self.lanes = spmv_lanes(nrows, nnz)
+        self.cg_iterations = None
+        self._col32 = None
+
+    @property
+    def size(self):
+        return self.shape[0] * self.shape[1]
+
+    # -- device side
+
+    def triplet(self):
+        '''(values, rowptr, colidx) as device tensors'''
+        if self._dev is None:
+            from . import device
+            values, rowptr, colidx = self._hostcsr
+            self._dev = device.to_dev(values, 'float64'), device.to_dev(rowptr, 'int64'), device.to_dev(colidx, 'int64')
+        return self._dev
+
+    def _columns(self):
+        '''the int32 column indices, made at the first product; None for matrices too wide for them'''
+        if self._col32 is None and self._ncols <= 0x7fffffff and self.nnz:
+            from . import kernels
+            self._col32 = kernels.csr_compact(self.triplet()[2], self._ncols)
+        return self._col32
+
+    def _with_values(self, values):
+        '''a matrix on the same index tensors (and their int32 copy)'''
+        _, rowptr, colidx = self.triplet()
+        new = HipMatrix(values, rowptr, colidx, self._ncols)
+        new._col32 = self._col32
+        return new
+
+    def spmv(self, x, *, alpha=1., beta=0., b=None, rowmask=None, y=None, lanes=None):
+        '''y = mask(alpha A x + beta b) on device tensors (nh_csr_spmv); `b` may be `y`'''
+        from . import kernels
+        values, rowptr, colidx = self.triplet()
+        return kernels.csr_spmv(values, rowptr, colidx, self._ncols, x, y=y, alpha=alpha, beta=beta, b=b, rowmask=rowmask, col32=self._columns(),
+                                lanes=self.lanes if lanes is None else lanes)
+
+    def __matmul__(self, other):
+        '''A @ x for one vector: a numpy vector gives a numpy vector, a device tensor a device tensor'''
+        on_device = _is_tensor(other)
+        if not on_device:
+            other = numpy.asarray(other, dtype=float)
+        if other.ndim != 1 or other.shape[0] != self.shape[1]:
+            raise MatrixError(f'cannot multiply a {self.shape[0]}x{self.shape[1]} matrix with an array of shape {tuple(other.shape)}')
+        from . import device
+        y = self.spmv(other.contiguous() if on_device else device.to_dev(other, 'float64'))
+        return y if on_device else device.to_host(y)
+
+    def _diagonal_dev(self):
+        from . import kernels
+        if self.shape[0] != self.shape[1]:
+            raise MatrixError('failed to extract diagonal: matrix is not square')
+        values, rowptr, colidx = self.triplet()
+        return kernels.csr_diagonal(values, rowptr, colidx, self._ncols, col32=self._col32)
+
+    def diagonal(self):
+        '''A_ii as a host vector, 0 where a row has no diagonal entry (Matrix.diagonal)'''
+        from . import device
+        return device.to_host(self._diagonal_dev())
+
+    # -- host side (PCIe)
+
+    def export(self, form):
+        '''host arrays: 'csr' (data, indices, indptr), 'coo' (data, (row, col)), 'dense'.  Copies the triplet over PCIe.'''
+        if form not in ('csr', 'coo', 'dense'):
+            raise NotImplementedError(f'cannot export HipMatrix to {form!r}')
+        if self._hostcsr is None:
+            from . import device
+            self._hostcsr = tuple(device.to_host(a) for a in self.triplet())  # (kept: the matrix is immutable)
+        values, rowptr, colidx = self._hostcsr
+        if form == 'csr':
+            return values, colidx, rowptr
+        if form == 'coo':
+            return values, (numpy.repeat(numpy.arange(self.shape[0], dtype=numpy.int64), numpy.diff(rowptr)), colidx)
+        return self._scipy().export('dense')
+
+    def _scipy(self):
+        data, indices, indptr = self.export('csr')
+        return _ScipyBackend.assemble(data, indptr, indices, self._ncols)
+
+    @staticmethod
+    def _from_scipy(core):
+        core = core.tocsr()
+        core.sum_duplicates()
+        core.sort_indices()
+        return HipMatrix(core.data, core.indptr.astype(numpy.int64), core.indices.astype(numpy.int64), core.shape[1])
+
+    def submatrix(self, rows, cols):
+        '''PCIe path: selected on the host by scipy and uploaded again.  A constrained `solve(solver='cg')` does not come here: it masks rows instead.'''
+        return self._from_scipy(self._scipy().submatrix(rows, cols).core)
+
+    @property
+    def T(self):
+        '''PCIe path: transposed on the host by scipy and uploaded again'''
+        return self._from_scipy(self._scipy().core.T)
+
+    # -- algebra: new values, shared indices
+
+    def __mul__(self, other):
+        if not numpy.isscalar(other):
+            return NotImplemented
+        return self._with_values(self.triplet()[0] * float(other))
+
+    __rmul__ = __mul__
+
+    def __truediv__(self, other):
+        return self.__mul__(1 / other)
+
+    def __neg__(self):
+        return self.__mul__(-1.)
+
+    def __add__(self, other, sign=1.):
+        if not isinstance(other, HipMatrix):
+            return NotImplemented
+        if self.shape != other.shape:
+            raise MatrixError(f'cannot add a {other.shape[0]}x{other.shape[1]} matrix to a {self.shape[0]}x{self.shape[1]} matrix')
+        a, b = self.triplet(), other.triplet()
+        if a[1] is b[1] and a[2] is b[2]:  # one pattern (scalar multiples, re-assemblies on the plan's index tensors): values only, on the device
+            return self._with_values(a[0] + b[0] if sign > 0 else a[0] - b[0])
+        core = self._scipy().core + sign * other._scipy().core  # PCIe path: different patterns are merged on the host
+        return self._from_scipy(core)
+
+    def __sub__(self, other):
+        return self.__add__(other, sign=-1.)
+
+    # -- solve
+
+    def solve(self, rhs=None, *, lhs0=None, constrain=None, solver='cg', atol=0., rtol=0., precon='diag', maxiter=None, check=16, **solverargs):
+        '''Solve A x = rhs with constraints in the reference's convention (`constraints`; Matrix.solve, matrix/_base.py:100-176).
+
+        solver='cg': conjugate gradients on the device for a SYMMETRIC POSITIVE DEFINITE matrix and ONE right-hand side.  No submatrix is formed: the free
+        dofs are a row mask, the residual mask(rhs - A lhs) is one masked product, and since residual and search direction vanish on the constrained dofs the
+        product ignores constrained columns by itself -- the iteration is that of the reference's submatrix(free, free).  It stops when the recurrence has
+        |r| <= max(atol, rtol |r0|); the true residual is then recomputed, and the iteration restarts from it should rounding have left it above the bound.
+        An iterative solve has no "machine precision" mode: atol = rtol = 0 is an error, not a request for it.  `precon`: 'diag' (Jacobi) or None.
+        `maxiter` defaults to the number of free dofs; `check`: iterations enqueued between two looks at the device's residual norm and breakdown flag (one
+        16-byte copy).  Raises ToleranceNotReached(best) when the bound is not met, MatrixError when the matrix turns out not to be positive definite.
+
+        Any other `solver` is a PCIe path: the matrix is exported to a ScipyMatrix and solved there.
+
+        Returns a numpy vector, or a device tensor if `rhs` was one.'''
+        nrows, ncols = self.shape
+        on_device = _is_tensor(rhs)
+        if rhs is not None:
+            if not on_device:
+                rhs = numpy.asarray(rhs, dtype=float)
+            if rhs.ndim != 1:
+                raise MatrixError(f'right-hand side has {rhs.ndim} axes: HipMatrix solves for one vector at a time')
+            if rhs.shape[0] != nrows:
+                raise MatrixError('right-hand side shape does not match matrix shape')
+        if nrows != ncols:
+            raise MatrixError(f'constrained matrix is not square: {nrows}x{ncols}')
+        if solver != 'cg':
+            x = self._scipy().solve(_host(rhs), lhs0=_host(lhs0), constrain=_host(constrain), **solverargs)
+            if on_device:
+                from . import device
+                x = device.to_dev(x, 'float64')
+            return x
+        if not (atol > 0 or rtol > 0):
+            raise MatrixError("solver 'cg' needs a tolerance: pass atol or rtol (an iterative solve has no machine-precision mode)")
+        if precon not in ('diag', None):
+            raise MatrixError(f'invalid preconditioner {precon!r} for HipMatrix: \'diag\' or None')
+        free, lhs = constraints(ncols, _host(constrain), _host(lhs0))
+        return self._cg(rhs, free, lhs, atol, rtol, precon, int(free.sum()) if maxiter is None else int(maxiter), max(1, int(check)), on_device)
+
+    def solve_leniently(self, *args, **kwargs):
+        '''`solve` that returns the vector reached instead of raising ToleranceNotReached'''
+        try:
+            return self.solve(*args, **kwargs)
+        except ToleranceNotReached as e:
+            import warnings
+            warnings.warn(str(e))
+            return e.best
+
+    def _cg(self, rhs, free, lhs, atol, rtol, precon, maxiter, check, on_device):
+        from . import device, kernels
+        n = self.shape[0]
+        values, rowptr, colidx = self.triplet()
+        mask = None if free.all() else device.to_dev(free, 'uint8')
+        x = device.to_dev(lhs, 'float64')
+        b = device.zeros(n, 'float64') if rhs is None else rhs.contiguous() if on_device else device.to_dev(rhs, 'float64')
+        dinv = None
+        if precon == 'diag':
+            diag = self._diagonal_dev()
+            keep = diag.new_ones(n, dtype=bool) if mask is None else mask != 0
+            if bool(((diag == 0) & keep).any()):
+                raise MatrixError("building 'diag' preconditioner: diagonal has zero entries")
+            dinv = (1. / diag).masked_fill(~keep | (diag == 0), 0.)  # (constrained rows: any finite number, their residual is zero)
+        r, p, q = (device.empty(n, 'float64') for _ in range(3))
+        work = kernels.cg_work()
+        result = (lambda: x) if on_device else (lambda: device.to_host(x))
+        bound, it = None, 0
+        while True:
+            self.cg_iterations = it  # (of the last solve, for whoever wants to know)
+            self.spmv(x, alpha=-1., beta=1., b=b, rowmask=mask, y=r)  # the true residual, mask(rhs - A x)
+            kernels.cg_init(dinv, r, p, work)
+            rr, _ = work[:2].tolist()
+            if bound is None:
+                bound = max(atol, rtol * rr ** .5)
+            if not numpy.isfinite(rr):
+                raise MatrixError('cg: non-finite residual')
+            if rr ** .5 <= bound:
+                return result()
+            if it >= maxiter:
+                raise ToleranceNotReached(result())
+            while it < maxiter:
+                steps = min(check, maxiter - it)
+                kernels.cg_iterate(values, rowptr, colidx, self._ncols, rowmask=mask, dinv=dinv, x=x, r=r, p=p, q=q, work=work, niter=steps, col32=self._columns(),
+                                   lanes=self.lanes)
+                it += steps
+                rr, flag = work[:2].tolist()
+                if flag:
+                    raise MatrixError('cg: matrix is not positive definite')
+                if not numpy.isfinite(rr):
+                    raise MatrixError('cg: non-finite residual')
+                if rr ** .5 <= bound:
+                    break
+
+
+class _HipBackend:
+    '''`matrix.backend('hip')`: host triplets (the hand-off of `function.eval(function.as_csr(K))`) become device matrices -- the round trip that
+    `function.as_matrix` avoids.'''
+
+    @staticmethod
+    def assemble(values, rowptr, colidx, ncols):
+        return HipMatrix(values, rowptr, colidx, ncols, validate=False)  # (`assemble_csr` has checked the triplet)
+
+    assemble_trusted = assemble
+
+
 class _Backend:
     '''``matrix.backend`` selector: any object with ``.assemble(values, rowptr,
     colidx, ncols)`` is accepted (matrix/__init__.py:20-27; fake-backend precedent
@@ -97,9 +426,9 @@ class _Backend:
     @contextlib.contextmanager
     def __call__(self, matrix):
         if isinstance(matrix, str):
-            if matrix.lower() not in ('scipy', 'auto'):
+            if matrix.lower() not in ('scipy', 'auto', 'hip'):
                 raise ValueError(f'matrix backend {matrix!r} is not available in nutils_amd')
-            matrix = _ScipyBackend
+            matrix = _HipBackend if matrix.lower() == 'hip' else _ScipyBackend
         if not hasattr(matrix, 'assemble'):
             raise ValueError('matrix backend does not have an assemble function')
         previous, _Backend.current = _Backend.current, matrix

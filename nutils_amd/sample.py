@@ -1613,7 +1613,7 @@ def evaluate(f, arguments):
     if isinstance(f, _Bound):
         return f.eval(arguments)
     if isinstance(f, function._AsCSR) and isinstance(f.integral, _factor0.FactoredMatrix):
-        return f.integral.as_csr()
+        return f.integral.as_matrix() if isinstance(f, function._AsMatrix) else f.integral.as_csr()
     if type(f) is function.Integral:
         bound = _bind_pvars(f.terms, arguments)
         if bound is not f.terms:
@@ -1627,6 +1627,8 @@ def evaluate(f, arguments):
         if not terms:
             raise ValueError('empty integral')
         values, rowptr, colidx, ncols = _MatrixPlan(terms).run(arguments)
+        if isinstance(f, function._AsMatrix):  # the triplet stays where it is
+            return _matrix.HipMatrix(values, rowptr, colidx, ncols)
         values, rowptr, colidx = device.to_host(values), device.to_host(rowptr), device.to_host(colidx)
         if isinstance(f, function._AsCOO):
             rowidx = numpy.repeat(numpy.arange(len(rowptr) - 1, dtype=numpy.int64), numpy.diff(rowptr))

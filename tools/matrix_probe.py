@@ -1,0 +1,206 @@
+'''Probe of the device-resident matrix backend (matrix.HipMatrix, nh_csr.hip): one JSON line per matrix with
+
+  * the time of a CSR product for every lanes-per-row count, from HIP events over windows of at least --window seconds after a warm-up, three windows
+    each (median, and the spread (max - min) / median the comparisons are read against),
+  * algorithmic bytes nnz (8 + 4) + nrows (8 + 8) + ncols 8 over that time, as a fraction of 8 TB/s (peak) and of 6.3 TB/s (achievable),
+  * torch's own CSR product (torch.sparse_csr_tensor(...) @ x) timed in the same process, its windows alternating with ours,
+  * what a user could do before this backend: device.to_host of the triplet plus the scipy product,
+  * the time of a CG iteration, the product's share of it, and iterations and wall time of a Jacobi-CG solve to rtol = 1e-8 with one side held.
+
+Usage: python tools/matrix_probe.py [--matrices poisson128,elasticity96,bilinear2048,p2vector32] [--scale 1.0] [--out FILE]
+(--scale shrinks every mesh for a quick look).  Not run by any test.'''
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+LANES = (4, 8, 16, 32, 64)
+
+
+def build(name, scale):
+    from nutils_amd import mesh, function
+    n = lambda full: max(2, int(round(full * scale)))
+    if name == 'poisson128':
+        shape, degree, vector = [n(128)] * 3, 1, False
+    elif name == 'elasticity96':
+        shape, degree, vector = [n(96)] * 3, 1, True
+    elif name == 'bilinear2048':
+        shape, degree, vector = [n(2048)] * 2, 1, False
+    elif name == 'p2vector32':
+        shape, degree, vector = [n(32)] * 3, 2, True
+    else:
+        raise SystemExit(f'unknown matrix {name!r}')
+    domain, geom = mesh.rectilinear([numpy.linspace(0, 1, m + 1) for m in shape])
+    nd = len(shape)
+    if vector:
+        u = domain.field('u', btype='std', degree=degree, shape=[nd])
+        v = domain.field('v', btype='std', degree=degree, shape=[nd])
+        eps = lambda w: function.symgrad(w, geom)
+        res = domain.integral(function.inner(eps(v), function.div(u, geom) * function.eye(nd) + 1.3 * eps(u)) * function.J(geom), degree=2 * degree)
+        K = function.derivative(function.derivative(res, 'v'), 'u')
+    else:
+        basis = domain.basis('std', degree=degree)
+        K = domain.integral(function.outer(function.grad(basis, geom)).sum(-1) * function.J(geom), degree=2 * degree)
+    nodes = [degree * m + 1 for m in shape]
+    held = numpy.zeros(nodes + [nd if vector else 1], dtype=bool)
+    held[0] = True  # the side x_0 = 0
+    return K, held.ravel(), dict(shape=shape, degree=degree, components=nd if vector else 1)
+
+
+def windows(fns, window, count=3):
+    '''per function: times per call [s] of `count` windows of at least `window` seconds; the windows of the functions alternate'''
+    import torch
+    reps = []
+    for fn in fns:
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        k = 0
+        while time.perf_counter() - t0 < .05:  # pilot
+            fn()
+            k += 1
+            torch.cuda.synchronize()
+        reps.append(max(3, int(k * window / .05 * 1.5)))
+    out = [[] for _ in fns]
+    for _ in range(count):
+        for i, fn in enumerate(fns):
+            while True:
+                start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                start.record()
+                for _ in range(reps[i]):
+                    fn()
+                stop.record()
+                stop.synchronize()
+                seconds = start.elapsed_time(stop) * 1e-3
+                if seconds >= window:
+                    break
+                reps[i] = int(reps[i] * max(1.5, 1.2 * window / max(seconds, 1e-6)))
+            out[i].append(seconds / reps[i])
+    return out
+
+
+def stats(times):
+    med = float(numpy.median(times))
+    return dict(us=med * 1e6, spread=float((max(times) - min(times)) / med))
+
+
+def probe(name, args):
+    import torch
+    import scipy.sparse
+    from nutils_amd import function, device, kernels, matrix
+    K, held, info = build(name, args.scale)
+    t0 = time.perf_counter()
+    A = function.eval(function.as_matrix(K))
+    device.synchronize()
+    info['assemble_first_ms'] = (time.perf_counter() - t0) * 1e3
+    values, rowptr, colidx = A.triplet()
+    nrows, ncols = A.shape
+    nnz = A.nnz
+    lengths = (rowptr[1:] - rowptr[:-1])
+    info.update(name=name, nrows=nrows, nnz=nnz, mean_row=nnz / nrows, max_row=int(lengths.max()), rule_lanes=A.lanes)
+    nbytes = nnz * 12 + nrows * 16 + ncols * 8
+    info['algorithmic_bytes'] = nbytes
+    x = torch.from_numpy(numpy.random.default_rng(0).normal(size=ncols)).cuda()
+    y = torch.empty(nrows, dtype=torch.float64, device='cuda')
+    A._columns()
+
+    # torch's CSR product
+    try:
+        T = torch.sparse_csr_tensor(rowptr, colidx, values, size=(nrows, ncols))
+        torch_fn = lambda: T @ x
+        err = float((torch_fn() - A.spmv(x)).abs().max() / A.spmv(x).abs().max())
+        info['torch_vs_ours_max_rel_diff'] = err
+    except Exception as e:  # not available in this build: recorded, not hidden
+        torch_fn = None
+        info['torch_csr'] = f'unavailable: {type(e).__name__}: {e}'
+
+    lanes = sorted(set(LANES) | {A.lanes})
+    fns = [(lambda L=L: A.spmv(x, y=y, lanes=L)) for L in lanes]
+    if torch_fn:
+        fns.append(torch_fn)
+    res = windows(fns, args.window)
+    info['spmv'] = {}
+    for L, t in zip(lanes, res):
+        s = stats(t)
+        s.update(frac_8TBs=nbytes / (s['us'] * 1e-6) / 8e12, frac_6p3TBs=nbytes / (s['us'] * 1e-6) / 6.3e12, GBs=nbytes / (s['us'] * 1e-6) / 1e9)
+        info['spmv'][str(L)] = s
+    best = min(info['spmv'], key=lambda L: info['spmv'][L]['us'])
+    info['best_lanes'] = int(best)
+    if torch_fn:
+        info['torch_csr'] = stats(res[-1])
+        ours = info['spmv'][str(A.lanes)]
+        info['ours_over_torch'] = ours['us'] / info['torch_csr']['us']
+    # int64 columns at the rule's lane count
+    fn64 = lambda: kernels.csr_spmv(values, rowptr, colidx, ncols, x, y=y, col32=None, lanes=A.lanes)
+    info['spmv_int64_columns'] = stats(windows([fn64], args.window)[0])
+
+    # what a user can do without the backend: copy the triplet, multiply with scipy
+    t0 = time.perf_counter()
+    hv, hrp, hci = (device.to_host(a) for a in (values, rowptr, colidx))
+    info['to_host_ms'] = (time.perf_counter() - t0) * 1e3
+    S = scipy.sparse.csr_matrix((hv, hci, hrp), (nrows, ncols))
+    xh = x.cpu().numpy()
+    S @ xh
+    t0 = time.perf_counter()
+    for _ in range(3):
+        S @ xh
+    info['scipy_matvec_ms'] = (time.perf_counter() - t0) / 3 * 1e3
+    del S, hv, hrp, hci
+
+    # CG: time per iteration, the product's share, a solve
+    free = ~held
+    mask = device.to_dev(free, 'uint8')
+    dinv = (1. / A._diagonal_dev()).masked_fill(mask == 0, 0.)
+    r = torch.from_numpy(numpy.random.default_rng(1).normal(size=nrows) * free).cuda()
+    xs, p, q = torch.zeros_like(r), torch.empty_like(r), torch.empty_like(r)
+    work = kernels.cg_work()
+    kernels.cg_init(dinv, r, p, work)
+    step = lambda: kernels.cg_iterate(values, rowptr, colidx, ncols, rowmask=mask, dinv=dinv, x=xs, r=r, p=p, q=q, work=work, niter=10, col32=A._columns(), lanes=A.lanes)
+    masked = lambda: A.spmv(p, y=q, rowmask=mask)
+    it, mv = windows([step, masked], args.window)
+    info['cg_iteration'] = stats([t / 10 for t in it])
+    info['cg_spmv_share'] = float(numpy.median(mv)) / info['cg_iteration']['us'] * 1e6
+    rhs = numpy.random.default_rng(2).normal(size=nrows)
+    rhs_dev = device.to_dev(rhs, 'float64')
+    device.synchronize()
+    t0 = time.perf_counter()
+    try:
+        sol = A.solve(rhs_dev, constrain=held, rtol=1e-8, maxiter=args.maxiter)
+        info['solve'] = dict(converged=True)
+    except matrix.ToleranceNotReached as e:
+        sol = e.best
+        info['solve'] = dict(converged=False)
+    device.synchronize()
+    info['solve'].update(wall_ms=(time.perf_counter() - t0) * 1e3, iterations=A.cg_iterations)
+    res0 = torch.where(mask != 0, rhs_dev, torch.zeros_like(rhs_dev))
+    info['solve']['true_relative_residual'] = float(A.spmv(sol, alpha=-1., beta=1., b=rhs_dev, rowmask=mask).norm() / res0.norm())
+    return info
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--matrices', default='poisson128,elasticity96,bilinear2048,p2vector32')
+    ap.add_argument('--scale', type=float, default=1.)
+    ap.add_argument('--window', type=float, default=.3)
+    ap.add_argument('--maxiter', type=int, default=20000)
+    ap.add_argument('--out', default=None)
+    args = ap.parse_args()
+    import torch
+    out = open(args.out, 'a') if args.out else None
+    for name in args.matrices.split(','):
+        line = json.dumps(probe(name, args))
+        print(line, flush=True)
+        if out:
+            out.write(line + '\n')
+            out.flush()
+        torch.cuda.empty_cache()
+
+
+if __name__ == '__main__':
+    main()
