@@ -709,6 +709,26 @@ int64_t nh_cg_work_doubles(void);
 int nh_cg_init(int64_t n, const double *dinv_dev, const double *r_dev, double *p_dev, double *work_dev, void *stream);
 int nh_cg_iterate(const nh_csr *A, const unsigned char *rowmask_dev, const double *dinv_dev, double *x_dev, double *r_dev, double *p_dev, double *q_dev,
                   double *work_dev, int niter, void *stream);
+/* Right-preconditioned BiCGStab for ANY square A (nonsymmetric, indefinite), M^-1 = dinv (Jacobi) or the identity (dinv_dev NULL), entirely on the
+ * device and by the rules of the CG above: constraints are a row mask on which every vector vanishes, nothing is atomic, no scalar visits the host,
+ * repeated solves are bit-identical.  An iteration is five launches: v = mask(A phat) with partial sums of rhat . v; alpha = rho / rhat . v, s = r - alpha v,
+ * shat = dinv s, partials of s . s; t = mask(A shat) with partials of t . s and t . t; omega = t . s / t . t, x += alpha phat + omega shat, r = s - omega t,
+ * partials of rhat . r and r . r; rho' = rhat . r, beta = (rho' / rho) (alpha / omega), p = r + beta (p - omega v), phat = dinv p.
+ * nh_bicgstab_init takes a given r and sets rhat = p = r (the first direction), phat = dinv r, the scalars, work[0 .. 2]; it marks the iteration as finished if
+ * r = 0.  nh_bicgstab_iterate enqueues niter iterations.  Once the recurrence has r . r <= stop_rr every remaining iteration, its products included, leaves all
+ * vectors as they are (iterated past convergence BiCGStab drives rho to 0, a false breakdown).  work_dev: nh_bicgstab_work_doubles() doubles, of which the
+ * host reads work[0] = r . r of the recurrence, work[1] = breakdown flag (0. / 1.), work[2] = iterations since nh_bicgstab_init that moved x (exact, whatever
+ * niter was).  The flag is raised, with r != 0, when rho' is 0 or not finite, rhat . v is 0 or not finite, t . t = 0 or omega is 0 or not finite while s . s > stop_rr,
+ * or alpha / beta overflow; x and r are then those of the last complete iteration and later iterations do no arithmetic (no 0 * inf).  No omega with
+ * s . s <= stop_rr (t = 0, say) is convergence at the half step: omega = 0, x += alpha phat, r = s.  Vectors: x, r in/out; rhat, p, v, s, t, phat, shat belong to the
+ * iteration between init and the last iterate; phat_dev / shat_dev are not used (and may be NULL) when dinv_dev is NULL; dinv must be finite on masked rows.
+ * nh_csr_spmv_dots is the product of the iteration on its own: y = mask(A x), then work[0] = w . y and work[1] = y . y from the per-workgroup partials, summed
+ * in the solver's order (work_dev: nh_bicgstab_work_doubles() doubles). */
+int64_t nh_bicgstab_work_doubles(void);
+int nh_csr_spmv_dots(const nh_csr *A, const double *x_dev, const double *w_dev, const unsigned char *rowmask_dev, double *y_dev, double *work_dev, void *stream);
+int nh_bicgstab_init(int64_t n, const double *dinv_dev, const double *r_dev, double *rhat_dev, double *p_dev, double *phat_dev, double *work_dev, void *stream);
+int nh_bicgstab_iterate(const nh_csr *A, const unsigned char *rowmask_dev, const double *dinv_dev, double *x_dev, double *r_dev, const double *rhat_dev, double *p_dev,
+                        double *v_dev, double *s_dev, double *t_dev, double *phat_dev, double *shat_dev, double *work_dev, double stop_rr, int niter, void *stream);
 
 #ifdef __cplusplus
 }

@@ -7,10 +7,14 @@
 //     in strides of L and the L partial sums are folded with __shfl_xor in a fixed order.  A workgroup strides over the rows, the grid
 //     is a function of (nrows, L) only, nothing is atomic: repeated calls are bit-identical.  Column indices are int32 (narrowed once
 //     per matrix by nh_csr_compact: 12 instead of 16 bytes per entry) or the int64 of the assembly; rowptr stays int64.
-//     DOT: additionally the workgroup's share of x . y goes to partial[blockIdx.x] (the p . Ap of a CG step).
+//     DOT = 1: additionally the workgroup's share of x . y goes to partial[blockIdx.x] (the p . Ap of a CG step).
+//     DOT = 2: the shares of w . y and y . y, w a vector of its own, go to partial[blockIdx.x] and partial2[blockIdx.x] (the two products of a BiCGStab
+//     step); the kernel does nothing at all when *skip != 0 (the iteration has stopped).
 //   * k_cg_update / k_cg_direction: the vector half of a CG step.  Every workgroup sums the partials of the kernel before it in the
 //     same order and so holds the same alpha / beta; scalars that cross an iteration live in two cells each, one written and one read
 //     per kernel, so no kernel reads a cell that one of its own workgroups writes.
+//   * k_bicgstab_half / k_bicgstab_update / k_bicgstab_direction: the vector part of a right-preconditioned BiCGStab step for general square matrices, by
+//     the same rules (the cells and who writes them: the B_ enum below).
 #include "nh_common.h"
 #include <algorithm>
 #include <climits>
@@ -41,13 +45,14 @@ __device__ __forceinline__ double partial_sum(const double *part, int n, double 
   return block_sum(s, lds);
 }
 
-template <int L, class Idx, bool DOT>
+template <int L, class Idx, int DOT>
 __global__ __launch_bounds__(WG) void k_csr_spmv(i64 nrows, const i64 *__restrict__ rowptr, const Idx *__restrict__ col, const double *__restrict__ values,
                                                  const double *__restrict__ x, double alpha, double beta, const double *b, const unsigned char *__restrict__ mask, double *y,
-                                                 double *partial) {
+                                                 double *partial, const double *__restrict__ w, double *partial2, const double *skip) {
+  if (DOT == 2 && skip && *skip != 0.) return;
   constexpr int G = WG / L;  // rows per workgroup and step
   const int lane = threadIdx.x & (L - 1);
-  double dot = 0;
+  double dot = 0, dot2 = 0;
   for (i64 base = (i64)blockIdx.x * G; base < nrows; base += (i64)gridDim.x * G) {  // (uniform trip count: every lane takes part in the shuffles)
     const i64 row = base + threadIdx.x / L;
     const bool live = row < nrows;
@@ -67,13 +72,21 @@ __global__ __launch_bounds__(WG) void k_csr_spmv(i64 nrows, const i64 *__restric
         if (b) v += beta * b[row];
       }
       y[row] = v;
-      if (DOT) dot += x[row] * v;
+      if (DOT == 1) dot += x[row] * v;
+      if (DOT == 2 && on) {
+        dot += w[row] * v;
+        dot2 += v * v;
+      }
     }
   }
   if (DOT) {
     __shared__ double lds[4];
     dot = block_sum(dot, lds);
-    if (threadIdx.x == 0) partial[blockIdx.x] = dot;
+    if (DOT == 2) dot2 = block_sum(dot2, lds);
+    if (threadIdx.x == 0) {
+      partial[blockIdx.x] = dot;
+      if (DOT == 2) partial2[blockIdx.x] = dot2;
+    }
   }
 }
 
@@ -178,6 +191,190 @@ __global__ __launch_bounds__(WG) void k_cg_direction(i64 n, int nparts, double *
   }
 }
 
+// ---- BiCGStab: right-preconditioned, M^-1 = dinv or the identity; all vectors vanish on masked rows.  An iteration is
+//   v = mask(A phat), partials of rhat . v                                          (k_csr_spmv, DOT = 2, w = rhat)
+//   half:      alpha = rho / rhat.v;  s = r - alpha v;  shat = dinv s;  partials of s . s
+//   t = mask(A shat), partials of t . s and t . t                                   (k_csr_spmv, DOT = 2, w = s)
+//   update:    omega = t.s / t.t;  x += alpha phat + omega shat;  r = s - omega t;  partials of rhat . r and r . r
+//   direction: rho' = rhat . r;  beta = (rho' / rho) (alpha / omega);  p = r + beta (p - omega v);  phat = dinv p
+// (the direction of the first iteration, p = r, is set by k_bicgstab_init).  Cells of the work array; after "<-" the kernel that writes a cell, every other
+// kernel only reads it.  B_RR, B_FLAG, B_COUNT are what the host looks at.  A status is 0 (iterate), ST_DONE (r . r <= stop_rr) or ST_BAD (breakdown); it
+// travels direction -> product, half -> product, update -> direction, and a kernel that receives a non-zero status passes it on and does nothing else.
+enum {
+  B_RR = 0,      // r . r of the recurrence        <- direction
+  B_FLAG = 1,    // 1. after a breakdown           <- direction
+  B_COUNT = 2,   // iterations that moved x        <- direction
+  B_ST = 3,      // status for product 1 and half  <- direction
+  B_ST_H = 4,    // status for product 2 and update <- half
+  B_ST_U = 5,    // status for direction           <- update
+  B_RHO = 6,     // rhat . r                       <- direction
+  B_RHO_OLD = 7, // the rho that alpha was made of <- half
+  B_ALPHA = 8,   //                                <- half
+  B_OMEGA = 9,   //                                <- update
+  B_COUNT_U = 10,  // B_COUNT, plus one if x moved <- update
+  B_WY = 16,                   // partials of w . y of a product
+  B_YY = B_WY + SPMV_MAX_WGS,  // partials of y . y of a product
+  B_SS = B_YY + SPMV_MAX_WGS,  // partials of s . s    <- half
+  B_RHOP = B_SS + VEC_MAX_WGS, // partials of rhat . r <- update
+  B_RRP = B_RHOP + VEC_MAX_WGS,  // partials of r . r  <- update, init
+  B_END = B_RRP + VEC_MAX_WGS
+};
+constexpr double ST_DONE = 1., ST_BAD = 2.;
+
+__device__ __forceinline__ bool finite(double a) { return a >= -1.7976931348623157e308 && a <= 1.7976931348623157e308; }
+
+// rhat = p = r, phat = dinv r, partials of r . r
+__global__ __launch_bounds__(WG) void k_bicgstab_init(i64 n, double *work, const double *__restrict__ dinv, const double *__restrict__ r, double *__restrict__ rhat,
+                                                      double *__restrict__ p, double *__restrict__ phat) {
+  __shared__ double lds[4];
+  double rr = 0;
+  for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < n; i += (i64)gridDim.x * WG) {
+    const double ri = r[i];
+    rhat[i] = ri;
+    p[i] = ri;
+    if (dinv) phat[i] = dinv[i] * ri;
+    rr += ri * ri;
+  }
+  rr = block_sum(rr, lds);
+  if (threadIdx.x == 0) work[B_RRP + blockIdx.x] = rr;
+}
+
+__global__ __launch_bounds__(WG) void k_bicgstab_init_scalars(int nparts, double *work) {
+  __shared__ double lds[4];
+  const double rr = partial_sum(work + B_RRP, nparts, lds);
+  if (threadIdx.x == 0) {
+    const bool bad = !finite(rr);
+    work[B_RR] = rr;
+    work[B_FLAG] = bad ? 1. : 0.;
+    work[B_COUNT] = 0.;
+    work[B_ST] = bad ? ST_BAD : rr == 0. ? ST_DONE : 0.;  // (a residual of zero: nothing to do, and rhat . v = 0 would be no breakdown)
+    work[B_RHO] = rr;                                     // rhat = r
+    work[B_RHO_OLD] = work[B_ALPHA] = work[B_OMEGA] = 1.;
+  }
+}
+
+// reads ST, RHO, the rhat . v partials; writes ST_H, RHO_OLD, ALPHA, the s . s partials.  shat is not written without a preconditioner (it is s).
+__global__ __launch_bounds__(WG) void k_bicgstab_half(i64 n, int nwy, double *work, const double *__restrict__ dinv, const double *__restrict__ r, const double *__restrict__ v,
+                                                      double *__restrict__ s, double *__restrict__ shat) {
+  __shared__ double lds[4];
+  const double st = work[B_ST];
+  if (st != 0.) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) work[B_ST_H] = st;
+    return;
+  }
+  const double rv = partial_sum(work + B_WY, nwy, lds);
+  const double rho = work[B_RHO];
+  const double alpha = rv != 0. ? rho / rv : 0.;
+  const bool bad = !(rv != 0. && finite(rv) && finite(alpha));
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    work[B_ST_H] = bad ? ST_BAD : 0.;
+    work[B_RHO_OLD] = rho;
+    work[B_ALPHA] = alpha;
+  }
+  if (bad) return;
+  double ss = 0;
+  for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < n; i += (i64)gridDim.x * WG) {
+    const double si = r[i] - alpha * v[i];
+    s[i] = si;
+    if (dinv) shat[i] = dinv[i] * si;
+    ss += si * si;
+  }
+  ss = block_sum(ss, lds);
+  if (threadIdx.x == 0) work[B_SS + blockIdx.x] = ss;
+}
+
+// reads ST_H, ALPHA, COUNT, the t . s, t . t and s . s partials; writes ST_U, OMEGA, COUNT_U, the rhat . r and r . r partials
+__global__ __launch_bounds__(WG) void k_bicgstab_update(i64 n, int nwy, int nparts, double stop_rr, double *work, double *__restrict__ x, double *__restrict__ r,
+                                                        const double *__restrict__ rhat, const double *phat, const double *shat, const double *s,
+                                                        const double *__restrict__ t) {
+  __shared__ double lds[4];
+  const double st = work[B_ST_H], count = work[B_COUNT];
+  if (st != 0.) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      work[B_ST_U] = st;
+      work[B_COUNT_U] = count;
+    }
+    return;
+  }
+  const double ts = partial_sum(work + B_WY, nwy, lds);
+  const double tt = partial_sum(work + B_YY, nwy, lds);
+  const double ss = partial_sum(work + B_SS, nparts, lds);
+  const double alpha = work[B_ALPHA];
+  double omega = tt != 0. ? ts / tt : 0.;
+  bool bad = false;
+  if (!(omega != 0. && finite(omega))) {  // no second half: with s within the bound that is convergence at the half step, x += alpha phat, r = s
+    omega = 0.;
+    bad = !(ss <= stop_rr);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    work[B_ST_U] = bad ? ST_BAD : 0.;
+    work[B_OMEGA] = omega;
+    work[B_COUNT_U] = bad ? count : count + 1.;
+  }
+  if (bad) return;
+  double rho = 0, rr = 0;
+  for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < n; i += (i64)gridDim.x * WG) {
+    x[i] += alpha * phat[i] + omega * shat[i];
+    const double ri = s[i] - omega * t[i];
+    r[i] = ri;
+    rho += rhat[i] * ri;
+    rr += ri * ri;
+  }
+  rho = block_sum(rho, lds);
+  rr = block_sum(rr, lds);
+  if (threadIdx.x == 0) {
+    work[B_RHOP + blockIdx.x] = rho;
+    work[B_RRP + blockIdx.x] = rr;
+  }
+}
+
+// reads ST_U, RHO_OLD, ALPHA, OMEGA, COUNT_U, the rhat . r and r . r partials; writes RR, FLAG, COUNT, ST, RHO.  phat is not written without a
+// preconditioner (it is p).
+__global__ __launch_bounds__(WG) void k_bicgstab_direction(i64 n, int nparts, double stop_rr, double *work, const double *__restrict__ dinv, const double *__restrict__ r,
+                                                           const double *__restrict__ v, double *__restrict__ p, double *__restrict__ phat) {
+  __shared__ double lds[4];
+  const double st = work[B_ST_U], count = work[B_COUNT_U];
+  const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+  if (st != 0.) {
+    if (first) {
+      work[B_ST] = st;
+      work[B_COUNT] = count;
+      if (st == ST_BAD) work[B_FLAG] = 1.;
+    }
+    return;
+  }
+  const double rho = partial_sum(work + B_RHOP, nparts, lds);
+  const double rr = partial_sum(work + B_RRP, nparts, lds);
+  const double omega = work[B_OMEGA];
+  const bool done = rr <= stop_rr;
+  const double beta = done || omega == 0. ? 0. : (rho / work[B_RHO_OLD]) * (work[B_ALPHA] / omega);
+  const bool bad = !done && !(rho != 0. && finite(rho) && omega != 0. && finite(beta));
+  if (first) {
+    work[B_RR] = rr;
+    work[B_COUNT] = count;
+    work[B_ST] = done ? ST_DONE : bad ? ST_BAD : 0.;
+    if (bad) work[B_FLAG] = 1.;
+    work[B_RHO] = rho;
+  }
+  if (done || bad) return;
+  for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < n; i += (i64)gridDim.x * WG) {
+    const double pi = r[i] + beta * (p[i] - omega * v[i]);
+    p[i] = pi;
+    if (dinv) phat[i] = dinv[i] * pi;
+  }
+}
+
+// work[0] = w . y, work[1] = y . y from the partials of a product, summed in the order the solver's kernels use
+__global__ __launch_bounds__(WG) void k_spmv_dots_sum(int nwy, double *work) {
+  __shared__ double lds[4];
+  const double wy = partial_sum(work + B_WY, nwy, lds);
+  const double yy = partial_sum(work + B_YY, nwy, lds);
+  if (threadIdx.x == 0) {
+    work[0] = wy;
+    work[1] = yy;
+  }
+}
+
 bool lanes_ok(int lanes) { return lanes >= 0 && lanes <= 64 && (lanes & (lanes - 1)) == 0; }
 
 int check_csr(const char *who, const nh_csr *A) {
@@ -193,36 +390,49 @@ int check_csr(const char *who, const nh_csr *A) {
 unsigned spmv_grid(i64 nrows, int L) { return (unsigned)std::min<i64>((nrows + WG / L - 1) / (WG / L), SPMV_MAX_WGS); }
 unsigned vec_grid(i64 n) { return (unsigned)std::min<i64>((n + WG - 1) / WG, VEC_MAX_WGS); }
 
+// what a product leaves besides y: nothing (partial == NULL), the partials of x . y (w == NULL), or those of w . y and y . y
+struct Epilogue {
+  double *partial = nullptr;
+  const double *w = nullptr;
+  double *partial2 = nullptr;
+  const double *skip = nullptr;
+};
+
 template <int L, class Idx>
-void launch_lanes(const nh_csr *A, const Idx *col, double alpha, const double *x, double beta, const double *b, const unsigned char *mask, double *y, double *partial,
+void launch_lanes(const nh_csr *A, const Idx *col, double alpha, const double *x, double beta, const double *b, const unsigned char *mask, double *y, const Epilogue &e,
                   hipStream_t s) {
   const dim3 grid(spmv_grid(A->nrows, L));
-  if (partial)
-    hipLaunchKernelGGL((k_csr_spmv<L, Idx, true>), grid, dim3(WG), 0, s, (i64)A->nrows, (const i64 *)A->rowptr_dev, col, A->values_dev, x, alpha, beta, b, mask, y, partial);
+  if (e.w)
+    hipLaunchKernelGGL((k_csr_spmv<L, Idx, 2>), grid, dim3(WG), 0, s, (i64)A->nrows, (const i64 *)A->rowptr_dev, col, A->values_dev, x, alpha, beta, b, mask, y, e.partial, e.w,
+                       e.partial2, e.skip);
+  else if (e.partial)
+    hipLaunchKernelGGL((k_csr_spmv<L, Idx, 1>), grid, dim3(WG), 0, s, (i64)A->nrows, (const i64 *)A->rowptr_dev, col, A->values_dev, x, alpha, beta, b, mask, y, e.partial, e.w,
+                       e.partial2, e.skip);
   else
-    hipLaunchKernelGGL((k_csr_spmv<L, Idx, false>), grid, dim3(WG), 0, s, (i64)A->nrows, (const i64 *)A->rowptr_dev, col, A->values_dev, x, alpha, beta, b, mask, y, partial);
+    hipLaunchKernelGGL((k_csr_spmv<L, Idx, 0>), grid, dim3(WG), 0, s, (i64)A->nrows, (const i64 *)A->rowptr_dev, col, A->values_dev, x, alpha, beta, b, mask, y, e.partial, e.w,
+                       e.partial2, e.skip);
 }
 
 template <class Idx>
-void launch_idx(int L, const nh_csr *A, const Idx *col, double alpha, const double *x, double beta, const double *b, const unsigned char *mask, double *y, double *partial,
+void launch_idx(int L, const nh_csr *A, const Idx *col, double alpha, const double *x, double beta, const double *b, const unsigned char *mask, double *y, const Epilogue &e,
                 hipStream_t s) {
   switch (L) {
-    case 1: launch_lanes<1>(A, col, alpha, x, beta, b, mask, y, partial, s); break;
-    case 2: launch_lanes<2>(A, col, alpha, x, beta, b, mask, y, partial, s); break;
-    case 4: launch_lanes<4>(A, col, alpha, x, beta, b, mask, y, partial, s); break;
-    case 8: launch_lanes<8>(A, col, alpha, x, beta, b, mask, y, partial, s); break;
-    case 16: launch_lanes<16>(A, col, alpha, x, beta, b, mask, y, partial, s); break;
-    case 32: launch_lanes<32>(A, col, alpha, x, beta, b, mask, y, partial, s); break;
-    default: launch_lanes<64>(A, col, alpha, x, beta, b, mask, y, partial, s); break;
+    case 1: launch_lanes<1>(A, col, alpha, x, beta, b, mask, y, e, s); break;
+    case 2: launch_lanes<2>(A, col, alpha, x, beta, b, mask, y, e, s); break;
+    case 4: launch_lanes<4>(A, col, alpha, x, beta, b, mask, y, e, s); break;
+    case 8: launch_lanes<8>(A, col, alpha, x, beta, b, mask, y, e, s); break;
+    case 16: launch_lanes<16>(A, col, alpha, x, beta, b, mask, y, e, s); break;
+    case 32: launch_lanes<32>(A, col, alpha, x, beta, b, mask, y, e, s); break;
+    default: launch_lanes<64>(A, col, alpha, x, beta, b, mask, y, e, s); break;
   }
 }
 
-int spmv(const nh_csr *A, double alpha, const double *x, double beta, const double *b, const unsigned char *mask, double *y, double *partial, hipStream_t s) {
+int spmv(const nh_csr *A, double alpha, const double *x, double beta, const double *b, const unsigned char *mask, double *y, const Epilogue &e, hipStream_t s) {
   const int L = A->lanes ? A->lanes : nh_csr_lanes(A->nrows, A->nnz);
   if (A->col32_dev)
-    launch_idx(L, A, A->col32_dev, alpha, x, beta, b, mask, y, partial, s);
+    launch_idx(L, A, A->col32_dev, alpha, x, beta, b, mask, y, e, s);
   else
-    launch_idx(L, A, (const i64 *)A->colidx_dev, alpha, x, beta, b, mask, y, partial, s);
+    launch_idx(L, A, (const i64 *)A->colidx_dev, alpha, x, beta, b, mask, y, e, s);
   NH_LAUNCH_CHECK();
   return NH_OK;
 }
@@ -260,7 +470,7 @@ int nh_csr_spmv(const nh_csr *A, double alpha, const double *x_dev, double beta,
     NH_CHECK_HIP(hipMemsetAsync(y_dev, 0, sizeof(double) * (size_t)A->nrows, nh_stream(stream)));
     return NH_OK;
   }
-  return spmv(A, alpha, x_dev, beta, b_dev, rowmask_dev, y_dev, nullptr, nh_stream(stream));
+  return spmv(A, alpha, x_dev, beta, b_dev, rowmask_dev, y_dev, Epilogue(), nh_stream(stream));
 }
 
 int nh_csr_diagonal(const nh_csr *A, double *diag_dev, void *stream) {
@@ -307,11 +517,82 @@ int nh_cg_iterate(const nh_csr *A, const unsigned char *rowmask_dev, const doubl
   const unsigned grid = vec_grid(n);
   nh_csr B = *A;
   B.lanes = L;
+  Epilogue pq;
+  pq.partial = work_dev + W_PQ;
   for (int it = 0; it < niter; ++it) {
-    if (int rc = spmv(&B, 1., p_dev, 0., nullptr, rowmask_dev, q_dev, work_dev + W_PQ, s)) return rc;
+    if (int rc = spmv(&B, 1., p_dev, 0., nullptr, rowmask_dev, q_dev, pq, s)) return rc;
     hipLaunchKernelGGL(k_cg_update, dim3(grid), dim3(WG), 0, s, n, npq, work_dev, dinv_dev, x_dev, r_dev, (const double *)p_dev, (const double *)q_dev);
     NH_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_cg_direction, dim3(grid), dim3(WG), 0, s, n, (int)grid, work_dev, dinv_dev, (const double *)r_dev, p_dev);
+    NH_LAUNCH_CHECK();
+  }
+  return NH_OK;
+}
+
+int64_t nh_bicgstab_work_doubles(void) { return B_END; }
+
+int nh_csr_spmv_dots(const nh_csr *A, const double *x_dev, const double *w_dev, const unsigned char *rowmask_dev, double *y_dev, double *work_dev, void *stream) {
+  if (int rc = check_csr("nh_csr_spmv_dots", A)) return rc;
+  NH_REQUIRE(work_dev && (!A->nrows || (x_dev && w_dev && y_dev)), "nh_csr_spmv_dots: NULL vector");
+  if (!A->nrows) return NH_OK;
+  hipStream_t s = nh_stream(stream);
+  nh_csr B = *A;
+  B.lanes = A->lanes ? A->lanes : nh_csr_lanes(A->nrows, A->nnz);
+  Epilogue e;
+  e.partial = work_dev + B_WY;
+  e.w = w_dev;
+  e.partial2 = work_dev + B_YY;
+  if (int rc = spmv(&B, 1., x_dev, 0., nullptr, rowmask_dev, y_dev, e, s)) return rc;
+  hipLaunchKernelGGL(k_spmv_dots_sum, dim3(1), dim3(WG), 0, s, (int)spmv_grid(A->nrows, B.lanes), work_dev);
+  NH_LAUNCH_CHECK();
+  return NH_OK;
+}
+
+int nh_bicgstab_init(int64_t n, const double *dinv_dev, const double *r_dev, double *rhat_dev, double *p_dev, double *phat_dev, double *work_dev, void *stream) {
+  NH_REQUIRE(n >= 0, "nh_bicgstab_init: negative size");
+  NH_REQUIRE(work_dev && (!n || (r_dev && rhat_dev && p_dev && (!dinv_dev || phat_dev))), "nh_bicgstab_init: NULL vector");
+  const unsigned grid = vec_grid(n);
+  if (n) {
+    hipLaunchKernelGGL(k_bicgstab_init, dim3(grid), dim3(WG), 0, nh_stream(stream), (i64)n, work_dev, dinv_dev, r_dev, rhat_dev, p_dev, phat_dev);
+    NH_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_bicgstab_init_scalars, dim3(1), dim3(WG), 0, nh_stream(stream), (int)grid, work_dev);
+  NH_LAUNCH_CHECK();
+  return NH_OK;
+}
+
+int nh_bicgstab_iterate(const nh_csr *A, const unsigned char *rowmask_dev, const double *dinv_dev, double *x_dev, double *r_dev, const double *rhat_dev, double *p_dev,
+                        double *v_dev, double *s_dev, double *t_dev, double *phat_dev, double *shat_dev, double *work_dev, double stop_rr, int niter, void *stream) {
+  if (int rc = check_csr("nh_bicgstab_iterate", A)) return rc;
+  NH_REQUIRE(A->nrows == A->ncols, "nh_bicgstab_iterate: the matrix must be square (got %lld x %lld)", (long long)A->nrows, (long long)A->ncols);
+  NH_REQUIRE(niter >= 0, "nh_bicgstab_iterate: negative iteration count");
+  NH_REQUIRE(stop_rr >= 0., "nh_bicgstab_iterate: the bound on r . r must not be negative");
+  NH_REQUIRE(work_dev && (!A->nrows || (x_dev && r_dev && rhat_dev && p_dev && v_dev && s_dev && t_dev && (!dinv_dev || (phat_dev && shat_dev)))),
+             "nh_bicgstab_iterate: NULL vector");
+  if (!A->nrows) return NH_OK;
+  hipStream_t s = nh_stream(stream);
+  const i64 n = A->nrows;
+  nh_csr B = *A;
+  B.lanes = A->lanes ? A->lanes : nh_csr_lanes(A->nrows, A->nnz);
+  const int nwy = (int)spmv_grid(n, B.lanes);
+  const unsigned grid = vec_grid(n);
+  const double *ph = dinv_dev ? phat_dev : p_dev, *sh = dinv_dev ? shat_dev : s_dev;  // without a preconditioner phat is p and shat is s
+  Epilogue rv, ts;
+  rv.partial = ts.partial = work_dev + B_WY;
+  rv.partial2 = ts.partial2 = work_dev + B_YY;
+  rv.w = rhat_dev;
+  rv.skip = work_dev + B_ST;
+  ts.w = s_dev;
+  ts.skip = work_dev + B_ST_H;
+  for (int it = 0; it < niter; ++it) {
+    if (int rc = spmv(&B, 1., ph, 0., nullptr, rowmask_dev, v_dev, rv, s)) return rc;
+    hipLaunchKernelGGL(k_bicgstab_half, dim3(grid), dim3(WG), 0, s, n, nwy, work_dev, dinv_dev, (const double *)r_dev, (const double *)v_dev, s_dev, shat_dev);
+    NH_LAUNCH_CHECK();
+    if (int rc = spmv(&B, 1., sh, 0., nullptr, rowmask_dev, t_dev, ts, s)) return rc;
+    hipLaunchKernelGGL(k_bicgstab_update, dim3(grid), dim3(WG), 0, s, n, nwy, (int)grid, stop_rr, work_dev, x_dev, r_dev, rhat_dev, ph, sh, (const double *)s_dev,
+                       (const double *)t_dev);
+    NH_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_bicgstab_direction, dim3(grid), dim3(WG), 0, s, n, (int)grid, stop_rr, work_dev, dinv_dev, (const double *)r_dev, (const double *)v_dev, p_dev, phat_dev);
     NH_LAUNCH_CHECK();
   }
   return NH_OK;

@@ -862,3 +862,33 @@ def cg_iterate(values, rowptr, colidx, ncols, *, rowmask, dinv, x, r, p, q, work
     '''enqueue `niter` CG iterations (nh_cg_iterate): three launches each, nothing read back'''
     _lib.call('nh_cg_iterate', ctypes.byref(_csr(values, rowptr, colidx, ncols, col32, lanes)), device.ptr(rowmask), device.ptr(dinv), device.ptr(x), device.ptr(r),
               device.ptr(p), device.ptr(q), device.ptr(work), int(niter), device.stream())
+
+
+def bicgstab_work():
+    '''the work array of a BiCGStab solve (nh_bicgstab_work_doubles): [0] = r . r of the recurrence, [1] = breakdown flag, [2] = iterations since
+    `bicgstab_init` that moved x'''
+    return device.empty(_lib.load().nh_bicgstab_work_doubles(), 'float64')
+
+
+def csr_spmv_dots(values, rowptr, colidx, ncols, x, w, *, y=None, rowmask=None, col32=None, lanes=0, work=None):
+    '''the product of a BiCGStab iteration on its own (nh_csr_spmv_dots): y = mask(A x); returns (y, dots) with dots[0] = w . y and dots[1] = y . y, a view of
+    the first cells of `work`'''
+    if y is None:
+        y = device.empty(rowptr.numel() - 1, 'float64')
+    if work is None:
+        work = bicgstab_work()
+    _lib.call('nh_csr_spmv_dots', ctypes.byref(_csr(values, rowptr, colidx, ncols, col32, lanes)), device.ptr(x), device.ptr(w), device.ptr(rowmask), device.ptr(y),
+              device.ptr(work), device.stream())
+    return y, work[:2]
+
+
+def bicgstab_init(dinv, r, rhat, p, phat, work):
+    '''rhat = p = r, phat = dinv r, first r . r, flag and count cleared (nh_bicgstab_init); `phat` is None without a preconditioner'''
+    _lib.call('nh_bicgstab_init', r.numel(), device.ptr(dinv), device.ptr(r), device.ptr(rhat), device.ptr(p), device.ptr(phat), device.ptr(work), device.stream())
+
+
+def bicgstab_iterate(values, rowptr, colidx, ncols, *, rowmask, dinv, x, r, rhat, p, v, s, t, phat, shat, work, stop_rr, niter, col32=None, lanes=0):
+    '''enqueue `niter` BiCGStab iterations (nh_bicgstab_iterate): five launches each, nothing read back; they stop moving once r . r <= stop_rr'''
+    _lib.call('nh_bicgstab_iterate', ctypes.byref(_csr(values, rowptr, colidx, ncols, col32, lanes)), device.ptr(rowmask), device.ptr(dinv), device.ptr(x), device.ptr(r),
+              device.ptr(rhat), device.ptr(p), device.ptr(v), device.ptr(s), device.ptr(t), device.ptr(phat), device.ptr(shat), device.ptr(work), float(stop_rr), int(niter),
+              device.stream())

@@ -8,12 +8,14 @@ conditions) is the reference's.
 
 Two backends.  'scipy' (the default; 'auto' means the same) wraps the host copy
 of the triplet in a ``ScipyMatrix`` with a direct solver.  'hip' keeps the
-triplet in HBM as a ``HipMatrix``: products, the diagonal and a Jacobi-
-preconditioned conjugate-gradient solve for symmetric positive definite systems
+triplet in HBM as a ``HipMatrix``: products, the diagonal and two Jacobi-
+preconditioned Krylov solves -- conjugate gradients ('cg') for symmetric
+positive definite systems, BiCGStab ('bicgstab') for any square matrix --
 run on the device (nh_csr.hip); ``function.eval(function.as_matrix(K))`` builds
 one without the triplet ever visiting the host.  What a ``HipMatrix`` does
 through scipy and a re-upload -- ``submatrix``, ``T``, every solver other than
-'cg', sums of matrices with different patterns -- says so in its docstring.
+'cg' and 'bicgstab', sums of matrices with different patterns -- says so in its
+docstring.
 '''
 
 import contextlib
@@ -165,9 +167,10 @@ class HipMatrix:
     first use on the device.  The matrix keeps references and never writes into them.  At the first product the column indices are narrowed to int32 once
     (12 instead of 16 bytes per entry; matrices with more than 2^31 - 1 columns keep the int64 indices).
 
-    On the device: products (nh_csr_spmv), the diagonal, scalar multiples, sums of matrices that share their index tensors, and `solve(solver='cg')`, a
-    Jacobi-preconditioned conjugate-gradient iteration for SYMMETRIC POSITIVE DEFINITE systems with ONE right-hand side.  Through scipy and PCIe (export, host
-    operation, re-upload): `submatrix`, `T`, sums of matrices with different patterns, every other solver.'''
+    On the device: products (nh_csr_spmv), the diagonal, scalar multiples, sums of matrices that share their index tensors, `solve(solver='cg')`, a
+    Jacobi-preconditioned conjugate-gradient iteration for SYMMETRIC POSITIVE DEFINITE systems, and `solve(solver='bicgstab')`, a Jacobi-preconditioned
+    BiCGStab iteration for ANY square system (nonsymmetric, indefinite); both with ONE right-hand side.  `iterations` is the iteration count of the last device
+    solve.  Through scipy and PCIe (export, host operation, re-upload): `submatrix`, `T`, sums of matrices with different patterns, every other solver.'''
 
     def __init__(self, values, rowptr, colidx, ncols, *, validate=True):
         self._ncols = int(ncols)
@@ -186,6 +189,7 @@ class HipMatrix:
         self.nnz = nnz
         self.lanes = spmv_lanes(nrows, nnz)
         self.cg_iterations = None
+        self.iterations = None
         self._col32 = None
 
     @property
@@ -324,6 +328,11 @@ class HipMatrix:
         `maxiter` defaults to the number of free dofs; `check`: iterations enqueued between two looks at the device's residual norm and breakdown flag (one
         16-byte copy).  Raises ToleranceNotReached(best) when the bound is not met, MatrixError when the matrix turns out not to be positive definite.
 
+        solver='bicgstab': right-preconditioned BiCGStab on the device for ANY square matrix and ONE right-hand side, with the keywords, the row mask, the
+        stopping rule and the true-residual restart of 'cg'.  The iteration stops itself on the device, so `iterations` is exact whatever `check` is.  A
+        breakdown of the recurrence (a vanishing rhat . r, rhat . v, t . t or omega) after progress restarts it from the true residual with a fresh shadow
+        residual, the iterations counting on; a breakdown at the first step after a start raises MatrixError('bicgstab: breakdown').
+
         Any other `solver` is a PCIe path: the matrix is exported to a ScipyMatrix and solved there.
 
         Returns a numpy vector, or a device tensor if `rhs` was one.'''
@@ -338,18 +347,19 @@ class HipMatrix:
                 raise MatrixError('right-hand side shape does not match matrix shape')
         if nrows != ncols:
             raise MatrixError(f'constrained matrix is not square: {nrows}x{ncols}')
-        if solver != 'cg':
+        if solver not in ('cg', 'bicgstab'):
             x = self._scipy().solve(_host(rhs), lhs0=_host(lhs0), constrain=_host(constrain), **solverargs)
             if on_device:
                 from . import device
                 x = device.to_dev(x, 'float64')
             return x
         if not (atol > 0 or rtol > 0):
-            raise MatrixError("solver 'cg' needs a tolerance: pass atol or rtol (an iterative solve has no machine-precision mode)")
+            raise MatrixError(f"solver {solver!r} needs a tolerance: pass atol or rtol (an iterative solve has no machine-precision mode)")
         if precon not in ('diag', None):
             raise MatrixError(f'invalid preconditioner {precon!r} for HipMatrix: \'diag\' or None')
         free, lhs = constraints(ncols, _host(constrain), _host(lhs0))
-        return self._cg(rhs, free, lhs, atol, rtol, precon, int(free.sum()) if maxiter is None else int(maxiter), max(1, int(check)), on_device)
+        krylov = self._cg if solver == 'cg' else self._bicgstab
+        return krylov(rhs, free, lhs, atol, rtol, precon, int(free.sum()) if maxiter is None else int(maxiter), max(1, int(check)), on_device)
 
     def solve_leniently(self, *args, **kwargs):
         '''`solve` that returns the vector reached instead of raising ToleranceNotReached'''
@@ -360,10 +370,10 @@ class HipMatrix:
             warnings.warn(str(e))
             return e.best
 
-    def _cg(self, rhs, free, lhs, atol, rtol, precon, maxiter, check, on_device):
-        from . import device, kernels
+    def _krylov_setup(self, rhs, free, lhs, precon, on_device):
+        '''(mask, x, b, dinv) of a device solve: the row mask of the free dofs (None: all), the start vector, the right-hand side, the inverse diagonal'''
+        from . import device
         n = self.shape[0]
-        values, rowptr, colidx = self.triplet()
         mask = None if free.all() else device.to_dev(free, 'uint8')
         x = device.to_dev(lhs, 'float64')
         b = device.zeros(n, 'float64') if rhs is None else rhs.contiguous() if on_device else device.to_dev(rhs, 'float64')
@@ -374,12 +384,19 @@ class HipMatrix:
             if bool(((diag == 0) & keep).any()):
                 raise MatrixError("building 'diag' preconditioner: diagonal has zero entries")
             dinv = (1. / diag).masked_fill(~keep | (diag == 0), 0.)  # (constrained rows: any finite number, their residual is zero)
+        return mask, x, b, dinv
+
+    def _cg(self, rhs, free, lhs, atol, rtol, precon, maxiter, check, on_device):
+        from . import device, kernels
+        n = self.shape[0]
+        values, rowptr, colidx = self.triplet()
+        mask, x, b, dinv = self._krylov_setup(rhs, free, lhs, precon, on_device)
         r, p, q = (device.empty(n, 'float64') for _ in range(3))
         work = kernels.cg_work()
         result = (lambda: x) if on_device else (lambda: device.to_host(x))
         bound, it = None, 0
         while True:
-            self.cg_iterations = it  # (of the last solve, for whoever wants to know)
+            self.cg_iterations = self.iterations = it  # (of the last solve, for whoever wants to know)
             self.spmv(x, alpha=-1., beta=1., b=b, rowmask=mask, y=r)  # the true residual, mask(rhs - A x)
             kernels.cg_init(dinv, r, p, work)
             rr, _ = work[:2].tolist()
@@ -402,6 +419,44 @@ class HipMatrix:
                 if not numpy.isfinite(rr):
                     raise MatrixError('cg: non-finite residual')
                 if rr ** .5 <= bound:
+                    break
+
+    def _bicgstab(self, rhs, free, lhs, atol, rtol, precon, maxiter, check, on_device):
+        from . import device, kernels
+        n = self.shape[0]
+        values, rowptr, colidx = self.triplet()
+        mask, x, b, dinv = self._krylov_setup(rhs, free, lhs, precon, on_device)
+        r, rhat, p, v, s, t = (device.empty(n, 'float64') for _ in range(6))
+        phat, shat = (device.empty(n, 'float64') for _ in range(2)) if dinv is not None else (None, None)
+        work = kernels.bicgstab_work()
+        result = (lambda: x) if on_device else (lambda: device.to_host(x))
+        stop_rr, it = None, 0
+        while True:  # a start: from the true residual, with a fresh shadow residual
+            self.iterations = it
+            self.spmv(x, alpha=-1., beta=1., b=b, rowmask=mask, y=r)  # mask(rhs - A x)
+            kernels.bicgstab_init(dinv, r, rhat, p, phat, work)
+            rr = work[:1].item()
+            if stop_rr is None:
+                stop_rr = max(atol, rtol * rr ** .5) ** 2  # (the device compares r . r with this number, and so does the host)
+            if not numpy.isfinite(rr):
+                raise MatrixError('bicgstab: non-finite residual')
+            if rr <= stop_rr:
+                return result()
+            if it >= maxiter:
+                raise ToleranceNotReached(result())
+            start = it
+            while it < maxiter:
+                kernels.bicgstab_iterate(values, rowptr, colidx, self._ncols, rowmask=mask, dinv=dinv, x=x, r=r, rhat=rhat, p=p, v=v, s=s, t=t, phat=phat, shat=shat,
+                                         work=work, stop_rr=stop_rr, niter=min(check, maxiter - it), col32=self._columns(), lanes=self.lanes)
+                rr, flag, moved = work[:3].tolist()
+                self.iterations = it = start + int(moved)  # (the device counts the iterations that moved x: exact, not a multiple of `check`)
+                if flag:
+                    if not moved:
+                        raise MatrixError('bicgstab: breakdown')
+                    break  # restart from where the recurrence got to
+                if not numpy.isfinite(rr):
+                    raise MatrixError('bicgstab: non-finite residual')
+                if rr <= stop_rr:
                     break
 
 

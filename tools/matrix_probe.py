@@ -5,7 +5,11 @@
   * algorithmic bytes nnz (8 + 4) + nrows (8 + 8) + ncols 8 over that time, as a fraction of 8 TB/s (peak) and of 6.3 TB/s (achievable),
   * torch's own CSR product (torch.sparse_csr_tensor(...) @ x) timed in the same process, its windows alternating with ours,
   * what a user could do before this backend: device.to_host of the triplet plus the scipy product,
-  * the time of a CG iteration, the product's share of it, and iterations and wall time of a Jacobi-CG solve to rtol = 1e-8 with one side held.
+  * the time of a CG iteration, the product's share of it, and iterations and wall time of a Jacobi-CG solve to rtol = 1e-8 with one side held,
+  * for the nonsymmetric twin N = K + 0.5 (triu(K, 1) - tril(K, -1)), built on the device from the value tensor: the time of a BiCGStab iteration against
+    two products of the same run and against its vector passes at the stream rate, iterations, wall time and true residual of a Jacobi-BiCGStab solve under
+    the conditions of the CG solve, and (unless --no-host-solve) the route a user had before: device.to_host of the triplet, the free submatrix and
+    scipy.sparse.linalg.bicgstab with the same tolerance and Jacobi as a LinearOperator, timed once.
 
 Usage: python tools/matrix_probe.py [--matrices poisson128,elasticity96,bilinear2048,p2vector32] [--scale 1.0] [--out FILE]
 (--scale shrinks every mesh for a quick look).  Not run by any test.'''
@@ -180,7 +184,93 @@ def probe(name, args):
     info['solve'].update(wall_ms=(time.perf_counter() - t0) * 1e3, iterations=A.cg_iterations)
     res0 = torch.where(mask != 0, rhs_dev, torch.zeros_like(rhs_dev))
     info['solve']['true_relative_residual'] = float(A.spmv(sol, alpha=-1., beta=1., b=rhs_dev, rowmask=mask).norm() / res0.norm())
+    info['bicgstab'] = probe_bicgstab(A, free, mask, rhs_dev, res0, args)
     return info
+
+
+BICGSTAB_STEPS = 20
+
+
+def probe_bicgstab(A, free, mask, rhs_dev, res0, args):
+    '''the nonsymmetric twin of A: iteration time, a solve, the host route'''
+    import torch
+    import scipy.sparse
+    import scipy.sparse.linalg
+    from nutils_amd import device, kernels, matrix
+    values, rowptr, colidx = A.triplet()
+    nrows, ncols = A.shape
+    rows = torch.repeat_interleave(torch.arange(nrows, device=values.device), rowptr[1:] - rowptr[:-1])
+    N = A._with_values(values * (1 + .5 * torch.sign(colidx - rows)))  # set-up, not timed
+    del rows
+    nvalues = N.triplet()[0]
+    out = {}
+    dinv = (1. / N._diagonal_dev()).masked_fill(mask == 0, 0.)
+    r0 = torch.from_numpy(numpy.random.default_rng(1).normal(size=nrows) * free).cuda()
+    x, r, rhat, p, v, s, t, phat, shat = (torch.zeros_like(r0) for _ in range(9))
+    work = kernels.bicgstab_work()
+
+    def start():  # the same state before every timed call: the iteration must neither converge nor break down inside a window
+        x.zero_()
+        r.copy_(r0)
+        kernels.bicgstab_init(dinv, r, rhat, p, phat, work)
+
+    def steps():
+        start()
+        kernels.bicgstab_iterate(nvalues, rowptr, colidx, ncols, rowmask=mask, dinv=dinv, x=x, r=r, rhat=rhat, p=p, v=v, s=s, t=t, phat=phat, shat=shat, work=work, stop_rr=0.,
+                                 niter=BICGSTAB_STEPS, col32=A._columns(), lanes=A.lanes)
+
+    masked = lambda: N.spmv(phat, y=v, rowmask=mask)
+    t_steps, t_start, t_mv = windows([steps, start, masked], args.window)
+    steps()
+    rr, flag, moved = work[:3].tolist()
+    out['moved_per_call'], out['flag'] = moved, flag  # (BICGSTAB_STEPS and 0, or the time below is not that of an iteration)
+    per_iteration = [(a - b) / BICGSTAB_STEPS for a, b in zip(t_steps, t_start)]
+    out['iteration'] = stats(per_iteration)
+    out['masked_spmv'] = stats(t_mv)
+    out['iteration_over_two_products'] = out['iteration']['us'] / (2 * out['masked_spmv']['us'])
+    # vector passes of 8 n bytes: half r, v, dinv -> s, shat (5); update x, phat, shat, s, t, rhat -> x, r (8); direction r, p, v, dinv -> p, phat (6)
+    out['vector_passes'] = 19
+    vector_us = out['iteration']['us'] - 2 * out['masked_spmv']['us']
+    out['vector_part_us'] = vector_us
+    out['vector_part_frac_6p3TBs'] = 19 * 8 * nrows / (vector_us * 1e-6) / 6.3e12 if vector_us > 0 else None
+    del x, r, rhat, p, v, s, t, phat, shat
+
+    device.synchronize()
+    t0 = time.perf_counter()
+    try:
+        sol = N.solve(rhs_dev, constrain=~free, solver='bicgstab', rtol=1e-8, maxiter=args.maxiter)
+        out['solve'] = dict(converged=True)
+    except matrix.ToleranceNotReached as e:
+        sol = e.best
+        out['solve'] = dict(converged=False)
+    device.synchronize()
+    out['solve'].update(wall_ms=(time.perf_counter() - t0) * 1e3, iterations=N.iterations)
+    out['solve']['true_relative_residual'] = float(N.spmv(sol, alpha=-1., beta=1., b=rhs_dev, rowmask=mask).norm() / res0.norm())
+    del sol
+    if args.no_host_solve:
+        return out
+
+    # the route a user has without the device solver
+    t0 = time.perf_counter()
+    hv, hrp, hci = (device.to_host(a) for a in (nvalues, rowptr, colidx))
+    out['host'] = dict(to_host_ms=(time.perf_counter() - t0) * 1e3)
+    t0 = time.perf_counter()
+    S = scipy.sparse.csr_matrix((hv, hci, hrp), (nrows, ncols))
+    keep, = free.nonzero()
+    F = S[keep][:, keep]
+    b = rhs_dev.cpu().numpy()[keep]  # (the constrained values are zero: no lift)
+    d = 1. / F.diagonal()
+    jacobi = scipy.sparse.linalg.LinearOperator(F.shape, matvec=lambda y: d * y)
+    out['host']['submatrix_ms'] = (time.perf_counter() - t0) * 1e3
+    count = [0]
+    t0 = time.perf_counter()
+    try:
+        y, code = scipy.sparse.linalg.bicgstab(F, b, rtol=1e-8, atol=0., maxiter=args.maxiter, M=jacobi, callback=lambda _: count.__setitem__(0, count[0] + 1))
+    except TypeError:  # scipy before 1.12 calls the relative tolerance `tol`
+        y, code = scipy.sparse.linalg.bicgstab(F, b, tol=1e-8, atol=0., maxiter=args.maxiter, M=jacobi, callback=lambda _: count.__setitem__(0, count[0] + 1))
+    out['host'].update(bicgstab_ms=(time.perf_counter() - t0) * 1e3, iterations=count[0], converged=code == 0,
+                       true_relative_residual=float(numpy.linalg.norm(b - F @ y) / numpy.linalg.norm(b)))
+    return out
 
 
 def main():
@@ -189,6 +279,7 @@ def main():
     ap.add_argument('--scale', type=float, default=1.)
     ap.add_argument('--window', type=float, default=.3)
     ap.add_argument('--maxiter', type=int, default=20000)
+    ap.add_argument('--no-host-solve', action='store_true', help='skip the host BiCGStab of the nonsymmetric twin (minutes for the large matrices)')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     import torch
