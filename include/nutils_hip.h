@@ -700,11 +700,14 @@ int nh_csr_diagonal(const nh_csr *A, double *diag_dev, void *stream);
  * device: an iteration is three launches -- q = mask(A p) with partial sums of p . q per workgroup; alpha from the partials (summed by
  * every workgroup in the same order), x += alpha p, r -= alpha q, partials of r . z and r . r with z = dinv r; beta from those and
  * p = z + beta p -- and nothing is read back.  work_dev: nh_cg_work_doubles() doubles; after every iteration work[0] = r . r of the
- * recurrence and work[1] = the breakdown flag (0. / 1.): one 16-byte copy tells the host where the iteration stands.  The flag is raised
- * when r != 0 and p . q or r . z is not a positive finite number (A or the preconditioner is not positive definite); from then on the
- * iterations leave x, r and p as they are.  dinv_dev: inverse diagonal (Jacobi) or NULL (none); it must be finite, and r and p zero, on
- * masked rows.  nh_cg_init forms p = z = dinv r and the first r . z, r . r from a given r and clears the flag; nh_cg_iterate enqueues
- * niter iterations. */
+ * recurrence and work[1] = the breakdown flag (0. / 1.): one 16-byte copy tells the host where the iteration stands.  work[2] is the
+ * caller's to write after nh_cg_init (which sets it to 0.): the bound on r . r at or below which an iteration does no arithmetic and
+ * raises no flag.  A caller that enqueues several iterations between two looks at work[0] sets it to its stopping bound: iterated past
+ * convergence r . r falls through the subnormal range, where r . z or p . q is 0 before r . r is, a false breakdown.  The flag is raised
+ * when r . r > work[2] and p . q or r . z is not a positive finite number (A or the preconditioner is not positive definite); from then
+ * on the iterations leave x, r and p as they are.  dinv_dev: inverse diagonal (Jacobi) or NULL (none); it must be finite, and r and p
+ * zero, on masked rows.  nh_cg_init forms p = z = dinv r and the first r . z, r . r from a given r and clears the flag and the bound;
+ * nh_cg_iterate enqueues niter iterations. */
 int64_t nh_cg_work_doubles(void);
 int nh_cg_init(int64_t n, const double *dinv_dev, const double *r_dev, double *p_dev, double *work_dev, void *stream);
 int nh_cg_iterate(const nh_csr *A, const unsigned char *rowmask_dev, const double *dinv_dev, double *x_dev, double *r_dev, double *p_dev, double *q_dev,

@@ -25,8 +25,8 @@ constexpr int WG = 256;
 constexpr int SPMV_MAX_WGS = 2048;  // 8 waves per SIMD on 256 CUs; also the number of p . Ap partials every workgroup of k_cg_update sums
 constexpr int VEC_MAX_WGS = 1024;
 
-// cells of the CG work array (doubles)
-enum { W_RR = 0, W_FLAG_B = 1, W_FLAG_A = 2, W_RZ_A = 3, W_RZ_B = 4, W_PQ = 8, W_RZP = W_PQ + SPMV_MAX_WGS, W_RRP = W_RZP + VEC_MAX_WGS, W_END = W_RRP + VEC_MAX_WGS };
+// cells of the CG work array (doubles); the first three are the caller's to read (RR, FLAG_B) and to write (STOP: nh_cg_init clears it, the kernels only read it)
+enum { W_RR = 0, W_FLAG_B = 1, W_STOP = 2, W_FLAG_A = 3, W_RZ_A = 4, W_RZ_B = 5, W_PQ = 8, W_RZP = W_PQ + SPMV_MAX_WGS, W_RRP = W_RZP + VEC_MAX_WGS, W_END = W_RRP + VEC_MAX_WGS };
 
 // sum over the workgroup in a fixed order; every thread returns the total
 __device__ __forceinline__ double block_sum(double s, double *lds) {
@@ -132,18 +132,21 @@ __global__ __launch_bounds__(WG) void k_cg_init_scalars(int nparts, double *work
     work[W_RZ_A] = rz;
     work[W_FLAG_A] = 0.;
     work[W_FLAG_B] = 0.;
+    work[W_STOP] = 0.;
   }
 }
 
 // alpha = r.z / p.q;  x += alpha p;  r -= alpha q;  partials of r . z and r . r with z = dinv r.
-// reads RR, RZ_B, FLAG_A, the p.q partials; writes RZ_A, FLAG_B, the r.z / r.r partials
+// reads RR, RZ_B, FLAG_A, STOP, the p.q partials; writes RZ_A, FLAG_B, the r.z / r.r partials (not when done: r has not moved, they stand)
 __global__ __launch_bounds__(WG) void k_cg_update(i64 n, int npq, double *work, const double *__restrict__ dinv, double *__restrict__ x, double *__restrict__ r,
                                                   const double *__restrict__ p, const double *__restrict__ q) {
   __shared__ double lds[4];
   const double pq = partial_sum(work + W_PQ, npq, lds);
   const double rz = work[W_RZ_B], rr = work[W_RR];
   bool bad = work[W_FLAG_A] != 0.;
-  const bool done = rr == 0.;  // the residual vanished: nothing left to do, and p . q = 0 is no breakdown
+  // within the bound (0. without one: the residual vanished): nothing left to do, and p . q = 0 is no breakdown.  Iterated past convergence r . r falls
+  // through the subnormal range, where r . z or p . q underflow to 0 before r . r does: a false breakdown
+  const bool done = rr <= work[W_STOP];
   if (!done && !bad) bad = !(rz > 0. && rz <= 1.7976931348623157e308 && pq > 0. && pq <= 1.7976931348623157e308);
   const bool move = !done && !bad;
   const double alpha = move ? rz / pq : 0.;
@@ -151,6 +154,7 @@ __global__ __launch_bounds__(WG) void k_cg_update(i64 n, int npq, double *work, 
     work[W_RZ_A] = rz;
     work[W_FLAG_B] = bad ? 1. : 0.;
   }
+  if (done) return;
   double srz = 0, srr = 0;
   for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < n; i += (i64)gridDim.x * WG) {
     double ri = r[i];
@@ -171,7 +175,8 @@ __global__ __launch_bounds__(WG) void k_cg_update(i64 n, int npq, double *work, 
   }
 }
 
-// beta = r.z (new) / r.z (old);  p = z + beta p.  reads RZ_A, FLAG_B, the partials; writes RR, RZ_B, FLAG_A
+// beta = r.z (new) / r.z (old);  p = z + beta p (not once r . r is within the bound: no iteration will read p).  reads RZ_A, FLAG_B, STOP, the partials;
+// writes RR, RZ_B, FLAG_A
 __global__ __launch_bounds__(WG) void k_cg_direction(i64 n, int nparts, double *work, const double *__restrict__ dinv, const double *__restrict__ r, double *__restrict__ p) {
   __shared__ double lds[4];
   const double rz = partial_sum(work + W_RZP, nparts, lds);
@@ -183,7 +188,7 @@ __global__ __launch_bounds__(WG) void k_cg_direction(i64 n, int nparts, double *
     work[W_RZ_B] = bad ? rz_old : rz;
     work[W_FLAG_A] = bad ? 1. : 0.;
   }
-  if (bad) return;
+  if (bad || rr <= work[W_STOP]) return;
   const double beta = rz_old != 0. ? rz / rz_old : 0.;
   for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < n; i += (i64)gridDim.x * WG) {
     const double zi = dinv ? dinv[i] * r[i] : r[i];

@@ -849,17 +849,22 @@ def csr_diagonal(values, rowptr, colidx, ncols, *, col32=None):
 
 
 def cg_work():
-    '''the work array of a CG solve (nh_cg_work_doubles): [0] = r . r of the recurrence, [1] = breakdown flag'''
+    '''the work array of a CG solve (nh_cg_work_doubles): [0] = r . r of the recurrence, [1] = breakdown flag, [2] = the bound of `cg_stop`'''
     return device.empty(_lib.load().nh_cg_work_doubles(), 'float64')
 
 
 def cg_init(dinv, r, p, work):
-    '''p = z = dinv r, first r . z and r . r, flag cleared (nh_cg_init)'''
+    '''p = z = dinv r, first r . z and r . r, flag and bound cleared (nh_cg_init)'''
     _lib.call('nh_cg_init', r.numel(), device.ptr(dinv), device.ptr(r), device.ptr(p), device.ptr(work), device.stream())
 
 
+def cg_stop(work, stop_rr):
+    '''after `cg_init`: iterations that find r . r <= stop_rr do nothing (work[2] of nh_cg_iterate)'''
+    work[2:3].fill_(float(stop_rr))
+
+
 def cg_iterate(values, rowptr, colidx, ncols, *, rowmask, dinv, x, r, p, q, work, niter, col32=None, lanes=0):
-    '''enqueue `niter` CG iterations (nh_cg_iterate): three launches each, nothing read back'''
+    '''enqueue `niter` CG iterations (nh_cg_iterate): three launches each, nothing read back; they stop moving once r . r is within the bound of `cg_stop`'''
     _lib.call('nh_cg_iterate', ctypes.byref(_csr(values, rowptr, colidx, ncols, col32, lanes)), device.ptr(rowmask), device.ptr(dinv), device.ptr(x), device.ptr(r),
               device.ptr(p), device.ptr(q), device.ptr(work), int(niter), device.stream())
 

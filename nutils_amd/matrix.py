@@ -323,7 +323,8 @@ class HipMatrix:
         solver='cg': conjugate gradients on the device for a SYMMETRIC POSITIVE DEFINITE matrix and ONE right-hand side.  No submatrix is formed: the free
         dofs are a row mask, the residual mask(rhs - A lhs) is one masked product, and since residual and search direction vanish on the constrained dofs the
         product ignores constrained columns by itself -- the iteration is that of the reference's submatrix(free, free).  It stops when the recurrence has
-        |r| <= max(atol, rtol |r0|); the true residual is then recomputed, and the iteration restarts from it should rounding have left it above the bound.
+        |r| <= max(atol, rtol |r0|), and the iterations enqueued after that one do nothing; the true residual is then recomputed, and the iteration restarts from
+        it should rounding have left it above the bound.
         An iterative solve has no "machine precision" mode: atol = rtol = 0 is an error, not a request for it.  `precon`: 'diag' (Jacobi) or None.
         `maxiter` defaults to the number of free dofs; `check`: iterations enqueued between two looks at the device's residual norm and breakdown flag (one
         16-byte copy).  Raises ToleranceNotReached(best) when the bound is not met, MatrixError when the matrix turns out not to be positive definite.
@@ -394,20 +395,21 @@ class HipMatrix:
         r, p, q = (device.empty(n, 'float64') for _ in range(3))
         work = kernels.cg_work()
         result = (lambda: x) if on_device else (lambda: device.to_host(x))
-        bound, it = None, 0
+        stop_rr, it = None, 0
         while True:
             self.cg_iterations = self.iterations = it  # (of the last solve, for whoever wants to know)
             self.spmv(x, alpha=-1., beta=1., b=b, rowmask=mask, y=r)  # the true residual, mask(rhs - A x)
             kernels.cg_init(dinv, r, p, work)
             rr, _ = work[:2].tolist()
-            if bound is None:
-                bound = max(atol, rtol * rr ** .5)
+            if stop_rr is None:
+                stop_rr = max(atol, rtol * rr ** .5) ** 2  # (the device compares r . r with this number, and so does the host)
             if not numpy.isfinite(rr):
                 raise MatrixError('cg: non-finite residual')
-            if rr ** .5 <= bound:
+            if rr <= stop_rr:
                 return result()
             if it >= maxiter:
                 raise ToleranceNotReached(result())
+            kernels.cg_stop(work, stop_rr)  # (the iterations enqueued past convergence idle: their r . z would underflow before r . r, a false breakdown)
             while it < maxiter:
                 steps = min(check, maxiter - it)
                 kernels.cg_iterate(values, rowptr, colidx, self._ncols, rowmask=mask, dinv=dinv, x=x, r=r, p=p, q=q, work=work, niter=steps, col32=self._columns(),
@@ -418,7 +420,7 @@ class HipMatrix:
                     raise MatrixError('cg: matrix is not positive definite')
                 if not numpy.isfinite(rr):
                     raise MatrixError('cg: non-finite residual')
-                if rr ** .5 <= bound:
+                if rr <= stop_rr:
                     break
 
     def _bicgstab(self, rhs, free, lhs, atol, rtol, precon, maxiter, check, on_device):
