@@ -984,11 +984,7 @@ __global__ __launch_bounds__(LT2_EPB *(NBR / NBK)) __attribute__((amdgpu_waves_p
       double *cq = cbuf + buf * (QC * LT2_EPB * SS);
       if (NCB == 1 && q0) __syncthreads();  // (single buffer: phase B of the previous chunk has read it)
       const int q = q0 + wave;
-#ifdef NH_LT2_SKIPA  // (timing experiments only)
-      if (q < p.nq && p.nq < 0) {
-#else
       if (q < p.nq) {  // ---- phase A: (element = lane, point = q0 + wave)
-#endif
         double Ji[ND][ND], det;
         if (iso) {
           double J[ND][ND];
@@ -1169,11 +1165,7 @@ __global__ __launch_bounds__(LT2_EPB *(NBR / NBK)) __attribute__((amdgpu_waves_p
       }
       __syncthreads();
       // ---- phase B: (element, trial block) x the points of the chunk
-#ifdef NH_LT2_SKIPB
-      const int nqc = p.nq < 0 ? 1 : 0;
-#else
       const int nqc = min(QC, p.nq - q0);
-#endif
       for (int ql = 0; ql < nqc; ++ql) {
         const int qb = q0 + ql;
         const double *c = cq + ((size_t)ql * LT2_EPB + elB) * SS;

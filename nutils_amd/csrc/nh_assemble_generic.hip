@@ -220,11 +220,7 @@ __global__ __launch_bounds__(256) void k_matrix_generic(MatK p, FormK formarg) {
             for (int a = 0; a < S; ++a)
 #pragma unroll
               for (int b = 0; b < S; ++b) G[pp][a][b] = 0.;
-#ifdef NH_GEN_SKIPQ  // (timing experiments)
-          for (int q = q0; q < min(q1, q0 + 1); ++q) {
-#else
           for (int q = q0; q < q1; ++q) {
-#endif
             const double *Dq = Dt + (q - q0) * nbt * S;
             const double wq = Jw[q * JW + ND * ND];
 #pragma unroll
@@ -259,10 +255,6 @@ __global__ __launch_bounds__(256) void k_matrix_generic(MatK p, FormK formarg) {
                 for (int a = 0; a < S; ++a)
 #pragma unroll
                   for (int b = 0; b < S; ++b) acc += Cc[a * form.ncr * S + b] * G[pp][a][b];
-#ifdef NH_GEN_SKIPST
-                if (acc == 1.2345e300) p.local[0] = acc;
-                continue;
-#endif
                 if (p.local) {
                   double *dst = p.local + (emap0 + m * nbr + n) * (form.nct * form.ncr) + c * form.ncr + d;
                   *dst = q0 ? *dst + acc : acc;

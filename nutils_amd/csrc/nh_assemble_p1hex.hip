@@ -11,6 +11,8 @@
 //     numbering the sorted-unique pattern (evaluable.py:588-616) is the tensor product of per-axis ranges
 //     [max(X-1,0), min(X+1,N-1)], so rowptr(I,J,K) and the position of a column inside its row are pure arithmetic.
 // HBM traffic = vertex coordinates (each tile re-reads its lateral halo) + values.  Uniform meshes take k_p1hex_uniform instead.
+// Two kernels share the tile, the element routine (nh_p1hex_element.inc) and the launcher: k_p1hex_march (matrix with NH_P1HEX_KERNEL=march, and
+// the vector variant K u) and k_p1hex_skew (matrix, default), whose two halves alternate between arithmetic and memory role.
 #include "nh_common.h"
 #include <algorithm>
 #include <type_traits>
@@ -421,13 +423,8 @@ __device__ __forceinline__ void half_wait(unsigned *cnt, unsigned target) {
   asm volatile("" ::: "memory");
 }
 
-#ifdef NH_P1HEX_WPE  // experiment: tell the scheduler that two waves per SIMD is all there will ever be
-#define NH_WPE __attribute__((amdgpu_waves_per_eu(2, 2)))
-#else
-#define NH_WPE
-#endif
 template <int TJ, int TK, bool MASS, bool COEF>
-__global__ __launch_bounds__(2 * TJ * TK) NH_WPE void k_p1hex_skew(P1Args p) {
+__global__ __launch_bounds__(2 * TJ * TK) void k_p1hex_skew(P1Args p) {
   constexpr bool VEC = false;
 #ifdef NH_ABLATION
   long long tacc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tprev = clock64();
@@ -518,9 +515,6 @@ __global__ __launch_bounds__(2 * TJ * TK) NH_WPE void k_p1hex_skew(P1Args p) {
       htarget += G / 64;
       NH_TICK(0)
       const bool mathrole = ((s - (A - 1)) & 1) == grp;
-#ifdef NH_P1HEX_PRIO  // experiment: issue priority by role (1 = arithmetic wave first, 2 = memory wave first)
-      if (mathrole == (NH_P1HEX_PRIO == 1)) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0);
-#endif
       if (mathrole) {
         // ---- arithmetic role: element layer s -------------------------------------------------------------------------------
         const int ej = lt / TK, ek = lt % TK;
@@ -538,7 +532,7 @@ __global__ __launch_bounds__(2 * TJ * TK) NH_WPE void k_p1hex_skew(P1Args p) {
 #pragma unroll
         for (int k = 0; k < VPG; ++k) load_vertex(needv ? s + 2 : -1, lt + k * G, J0, K0, Vn[k]);
         const int P = s - 1;
-        bool arrived = false, staged = false, recycled = false;
+        bool arrived = false, staged = false;
         auto stage_vertices = [&]() {
 #pragma unroll
           for (int k = 0; k < VPG; ++k) {
@@ -565,47 +559,6 @@ __global__ __launch_bounds__(2 * TJ * TK) NH_WPE void k_p1hex_skew(P1Args p) {
               below = sl_ < 9;
               return (VK + ok_ + 1) * NS + (sl_ >= 13 ? sl_ - 13 : (dJ_ * VK + dK_) * NS + 13 - sl_);
             };
-#ifdef NH_P1HEX_PIPEFLUSH
-            // Per-LINE software pipeline: the LDS reads of line i + D are in flight while line i is stored, so the first store leaves ~1.5 k cycles
-            // earlier and the reads of the plane hide behind the (throughput-bound) stores instead of preceding them.  No exec region around the
-            // stores: the lanes beyond the 202 pairs of a line repeat lane 201 (same address, same data) -- a branch here would make the
-            // compiler's wait for the vertex loads BEHIND the stores a vmcnt(0), i.e. a wait for the whole flush to drain (the join of the skipped
-            // path has the loads as its youngest operations); straight-line, it is vmcnt(stores issued since), which only needs the loads.
-            constexpr int D = NH_P1HEX_PIPEFLUSH;
-            const int ec = 2 * min(lt, 201);
-            bool belowA, belowB;
-            const int offA = source(ec, belowA), offB = source(ec + 1, belowB);
-            const double *sA = acc + (belowA ? slot_of(P - 1) : slot_of(P)) + offA;
-            const double *sB = acc + (belowB ? slot_of(P - 1) : slot_of(P)) + offB;
-            const int li = lt - 202;
-            const bool lone = li >= 0 && li < OJ;
-            bool belowL;
-            const int offL = source(404, belowL);
-            const double aL = acc[(belowL ? slot_of(P - 1) : slot_of(P)) + offL + (lone ? li : 0) * (VK * NS)];
-            const i64 stride8 = 8 * (i64)(9 * (int)T2);
-            char *l0 = reinterpret_cast<char *>(p.values + ((3 * (i64)P - 1) * T1 * T2 + 3 * (cumJ0 * T2) + 9 * (3 * (i64)K0 - 1)));
-            char *lp = l0 + 8 * ec;
-            double a0[OJ], a1[OJ];
-#pragma unroll
-            for (int i = 0; i < D && i < OJ; ++i) a0[i] = sA[i * (VK * NS)], a1[i] = sB[i * (VK * NS)];
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int i = 0; i < OJ; ++i) {
-              if (i + D < OJ) a0[i + D] = sA[(i + D) * (VK * NS)], a1[i + D] = sB[(i + D) * (VK * NS)];
-              __builtin_amdgcn_sched_barrier(0);
-              const double2 v = make_double2(a0[i], a1[i]);
-              __builtin_memcpy(lp + i * stride8, &v, 16);
-              __builtin_amdgcn_sched_barrier(0);
-            }
-            half_arrive(hcnt);
-            arrived = true;
-            if (needv) {
-              stage_vertices();
-              staged = true;
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            if (lone) *reinterpret_cast<double *>(l0 + li * stride8 + 8 * 404) = aL;
-#else
             bool belowA, belowB;
             const int offA = source(e < 405 ? e : 404, belowA), offB = source(e + 1 < 405 ? e + 1 : 404, belowB);
             const double *sA = acc + (belowA ? slot_of(P - 1) : slot_of(P)) + offA;
@@ -635,26 +588,6 @@ __global__ __launch_bounds__(2 * TJ * TK) NH_WPE void k_p1hex_skew(P1Args p) {
             const i64 stride8 = 8 * (i64)(9 * (int)T2);
             char *l0 = reinterpret_cast<char *>(p.values + ((3 * (i64)P - 1) * T1 * T2 + 3 * (cumJ0 * T2) + 9 * (3 * (i64)K0 - 1)));
             char *lp = l0 + 16 * lt;
-#ifdef NH_P1HEX_INTERLEAVE
-            // the recycling of the slot of plane s-2 BETWEEN the stores: a store that finds the queue of the memory pipeline full stalls the wave, and the
-            // LDS writes placed behind all of them waited for the whole flush; one write behind each store goes out while the queue drains
-            half_wait(hcnt, htarget);
-            recycled = true;
-            {
-              double2 *z = reinterpret_cast<double2 *>(acc + slot_of(s - 2));
-              constexpr int NZ = (PS / 2 + G - 1) / G;
-              static_assert(NZ <= OJ, "one zeroing write per store");
-#pragma unroll
-              for (int i = 0; i < OJ; ++i) {
-                if (lt < 202) {
-                  const double2 v = make_double2(a0[i], a1[i]);
-                  __builtin_memcpy(lp + i * stride8, &v, 16);
-                }
-                if (i < NZ && lt + i * G < PS / 2) z[lt + i * G] = make_double2(0., 0.);
-                __builtin_amdgcn_sched_barrier(0);
-              }
-            }
-#else
             if (lt < 202) {
 #pragma unroll
               for (int i = 0; i < OJ; ++i) {
@@ -663,9 +596,7 @@ __global__ __launch_bounds__(2 * TJ * TK) NH_WPE void k_p1hex_skew(P1Args p) {
                 __builtin_memcpy(lp + i * stride8, &v, 16);  // 8-byte aligned 16-byte store
               }
             }
-#endif
             if (lone) *reinterpret_cast<double *>(l0 + li * stride8 + 8 * 404) = aL;
-#endif
           } else {
             // 32 lanes per row (27 slots), 8 rows per pass, two passes per K line
             constexpr int RPP = G / 32, KP = (OK + RPP - 1) / RPP;
@@ -719,9 +650,9 @@ __global__ __launch_bounds__(2 * TJ * TK) NH_WPE void k_p1hex_skew(P1Args p) {
         }
         NH_TICK(6)
         if (!arrived) half_arrive(hcnt);
-        if (!recycled) half_wait(hcnt, htarget);  // every wave of this half has read what it needs of plane s-2: recycle its slot
+        half_wait(hcnt, htarget);  // every wave of this half has read what it needs of plane s-2: recycle its slot
         NH_TICK(7)
-        if (!recycled) {
+        {
           double2 *z = reinterpret_cast<double2 *>(acc + slot_of(s - 2));
           for (int t = lt; t < PS / 2; t += G) z[t] = make_double2(0., 0.);
         }
@@ -745,9 +676,6 @@ __global__ __launch_bounds__(2 * TJ * TK) NH_WPE void k_p1hex_skew(P1Args p) {
 #endif
 }
 #undef NH_TICK
-
-#include "nh_p1hex_tiles.inc"
-#include "nh_p1hex_tri.inc"
 
 // ---- uniform geometry: all element matrices are equal (the reference hoists them out of the loop too) -------------
 // One thread evaluates the element matrix of the unit cell; the assembly is then a pure streaming kernel: every CSR entry is the
@@ -909,10 +837,9 @@ static int launch_march_inst(const nh_p1hex_args *a, P1Args &p, void *stream) {
   if (getenv("NH_P1HEX_MAXWG")) grid = std::min<unsigned>(grid, (unsigned)atoi(getenv("NH_P1HEX_MAXWG")));
 #endif
   auto kern = k_p1hex_march<TJ, TK, L, VEC, MASS, COEF>;
-  if constexpr (!VEC && L == 2) {  // the matrix goes through the skewed kernel (same tile, same LDS, same launch) unless NH_P1HEX_MARCH=1
-    const char *env = getenv("NH_P1HEX_MARCH"), *kenv = getenv("NH_P1HEX_KERNEL");  // (read per launch: the tests compare the kernels within one process)
-    const bool march = (env && atoi(env)) || (kenv && !strcmp(kenv, "march"));
-    if (!march) kern = k_p1hex_skew<TJ, TK, MASS, COEF>;
+  if constexpr (!VEC && L == 2) {  // the matrix goes through the skewed kernel (same tile, same LDS, same launch) unless NH_P1HEX_KERNEL=march
+    const char *env = getenv("NH_P1HEX_KERNEL");  // (read per launch: the tests compare the kernels within one process)
+    if (!(env && !strcmp(env, "march"))) kern = k_p1hex_skew<TJ, TK, MASS, COEF>;
   }
   static const void *attr_set[16][2] = {{nullptr, nullptr}};  // (this instantiation: the marching and the skewed kernel, per device)
   if (attr_set[dev][0] != (const void *)kern && attr_set[dev][1] != (const void *)kern) {
@@ -943,169 +870,6 @@ static int launch_march_inst(const nh_p1hex_args *a, P1Args &p, void *stream) {
   }
 #endif
   return NH_OK;
-}
-
-
-// ---- launch of the exact-tile kernel (matrix) ------------------------------------------------------------------------------------
-namespace {
-struct TileScratch {
-  void *base = nullptr;  // one allocation: ctl (64 B) | flags | flags_pro | exp | exp_pro
-  size_t cap = 0;
-  unsigned *err_host = nullptr, *err_dev = nullptr;
-};
-TileScratch g_tiles[16];  // per device
-}  // namespace
-
-int nh_p1hex_tiles_release(void) {
-  for (auto &t : g_tiles) {
-    if (t.base) NH_CHECK_HIP(hipFree(t.base));
-    t.base = nullptr, t.cap = 0;
-  }
-  return NH_OK;
-}
-
-template <bool MASS, bool COEF>
-static int launch_tiles_inst(const nh_p1hex_args *a, P1Args &p, void *stream) {
-  using namespace p1t;
-  int dev = 0;
-  NH_CHECK_HIP(hipGetDevice(&dev));
-  NH_REQUIRE(dev >= 0 && dev < 16, "nh_p1hex: device index %d not supported", dev);
-  static int cus_of[16] = {0};
-  static bool attr_set[16] = {false};
-  if (!cus_of[dev]) {
-    int n = 256;
-    NH_CHECK_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
-    cus_of[dev] = n;
-  }
-  auto kern = k_p1hex_tiles<MASS, COEF>;
-  if (!attr_set[dev]) {
-    NH_CHECK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES));
-    attr_set[dev] = true;
-  }
-  TileScratch &ts = g_tiles[dev];
-  if (!ts.err_host) {
-    NH_CHECK_HIP(hipHostMalloc((void **)&ts.err_host, sizeof(unsigned), hipHostMallocMapped));
-    *ts.err_host = 0;
-    NH_CHECK_HIP(hipHostGetDevicePointer((void **)&ts.err_dev, ts.err_host, 0));
-  }
-  static size_t layout[16][3] = {{0}};
-  if (*ts.err_host) {  // raised by an EARLIER launch (the word is read without synchronising)
-    *ts.err_host = 0;
-    layout[dev][0] = 0;  // the flag counts of that launch are incomplete: start over on zeroed flags
-    nh_set_error("nh_p1hex_laplace: a workgroup of an earlier launch timed out waiting for the tile faces of its neighbour -- are other kernels holding CUs? "
-                 "(NH_P1HEX_KERNEL=skew selects the kernel without inter-workgroup exchange)");
-    return NH_EHIP;
-  }
-  p.nbj = (p.n1 + T - 1) / T;
-  p.nbk = (p.n2 + T - 1) / T;
-  const int ncols = p.nbj * p.nbk, NPL = p.pl1 - p.pl0;
-  NH_REQUIRE(a->max_workgroups >= 0, "nh_p1hex: negative max_workgroups");
-  const int wgmax = a->max_workgroups ? std::min(cus_of[dev], a->max_workgroups) : cus_of[dev];
-  // plane segments per column: the same in every column (producer and consumer of a tile face work on the same plane at the same time);
-  // a run of n planes costs n + 3 slots
-  int nseg = 1;
-  {
-    static const int nseg_env = getenv("NH_P1HEX_NSEG") ? atoi(getenv("NH_P1HEX_NSEG")) : 0;
-    double best = 1e300;
-    for (int c = 1; c <= NPL; ++c) {
-      const i64 rounds = ((i64)ncols * c + wgmax - 1) / wgmax;
-      const double cost = (double)rounds * ((NPL + c - 1) / c + 3);
-      if (cost < best) best = cost, nseg = c;
-    }
-    if (nseg_env > 0) nseg = std::min(nseg_env, NPL);
-  }
-  const unsigned grid = (unsigned)std::min<i64>((i64)ncols * nseg, wgmax);
-  const size_t nflags = (size_t)ncols * NPL, nfpro = (size_t)ncols * nseg;
-  const size_t off_exp = tile_exp_offset(ncols, NPL, nseg), need = off_exp + (nflags + nfpro) * NEXP * sizeof(double);
-  // the layout depends on (ncols, NPL, nseg): a change of any of them restarts the epoch on zeroed flags
-  if (need > ts.cap || layout[dev][0] != nflags || layout[dev][1] != nfpro || layout[dev][2] != (size_t)NPL) {
-    NH_CHECK_HIP(hipStreamSynchronize(nh_stream(stream)));
-    if (need > ts.cap) {
-      if (ts.base) NH_CHECK_HIP(hipFree(ts.base));
-      ts.base = nullptr, ts.cap = 0;
-      NH_CHECK_HIP(hipMalloc(&ts.base, need));
-      ts.cap = need;
-    }
-    NH_CHECK_HIP(hipMemsetAsync(ts.base, 0, off_exp, nh_stream(stream)));
-    NH_CHECK_HIP(hipMemcpyAsync((char *)ts.base + 8, &ts.err_dev, sizeof(unsigned *), hipMemcpyHostToDevice, nh_stream(stream)));
-    static const unsigned always_raised = 0x7fffffffu;  // ctl[4]: the flag of a producer that does not exist
-    NH_CHECK_HIP(hipMemcpyAsync((char *)ts.base + 16, &always_raised, sizeof(unsigned), hipMemcpyHostToDevice, nh_stream(stream)));
-    NH_CHECK_HIP(hipStreamSynchronize(nh_stream(stream)));
-    layout[dev][0] = nflags, layout[dev][1] = nfpro, layout[dev][2] = (size_t)NPL;
-  }
-  TileArgs ta;
-  ta.base = (char *)ts.base;
-  ta.nseg = nseg;
-  ta.xcd = grid % 8 == 0 && !a->max_workgroups;
-#ifdef NH_ABLATION
-  p.debug = getenv("NH_P1HEX_DEBUG") ? atoi(getenv("NH_P1HEX_DEBUG")) : 0;
-  if (getenv("NH_P1HEX_NOXCD")) ta.xcd = 0;
-  static long long *tdbg = nullptr;
-  if (!tdbg) NH_CHECK_HIP(hipMalloc((void **)&tdbg, 16 * sizeof(long long)));
-  NH_CHECK_HIP(hipMemsetAsync(tdbg, 0, 16 * sizeof(long long), nh_stream(stream)));
-  p.tdbg = getenv("NH_P1HEX_TIMERS") ? tdbg : nullptr;
-#endif
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), LDS_BYTES, nh_stream(stream), p, ta);
-  NH_LAUNCH_CHECK();
-#ifdef NH_ABLATION
-  if (p.tdbg) {
-    long long h[16];
-    NH_CHECK_HIP(hipMemcpy(h, tdbg, sizeof h, hipMemcpyDeviceToHost));
-    const double nw = (double)grid * 4;  // waves per role
-    static int nprint = 0;
-    if (nprint++ < 3)
-      fprintf(stderr, "p1hex_tiles cycles per wave and slot (grid %u nseg %d, %.1f slots per role): MATH verts+routine %.0f | flags+imports %.0f | barrier %.0f || MEM import add+vertex loads+export+waits %.0f | "
-              "flush reads+flag+stage+stores %.0f | half wait+zero %.0f | barrier %.0f\n", grid, nseg, ((double)(p.pl1 - p.pl0) / nseg + 3) / 2,
-              h[2] / nw / (((double)(p.pl1 - p.pl0) / nseg + 3) / 2), h[3] / nw / (((double)(p.pl1 - p.pl0) / nseg + 3) / 2), h[11] / nw / (((double)(p.pl1 - p.pl0) / nseg + 3) / 2),
-              h[6] / nw / (((double)(p.pl1 - p.pl0) / nseg + 3) / 2), h[8] / nw / (((double)(p.pl1 - p.pl0) / nseg + 3) / 2), h[10] / nw / (((double)(p.pl1 - p.pl0) / nseg + 3) / 2),
-              h[12] / nw / (((double)(p.pl1 - p.pl0) / nseg + 3) / 2));
-  }
-#endif
-  return NH_OK;
-}
-
-// ---- launch of the three-role kernel (matrix) ---------------------------------------------------------------------------------------
-template <bool MASS, bool COEF>
-static int launch_tri_inst(const nh_p1hex_args *a, P1Args &p, void *stream) {
-  int dev = 0;
-  NH_CHECK_HIP(hipGetDevice(&dev));
-  NH_REQUIRE(dev >= 0 && dev < 16, "nh_p1hex: device index %d not supported", dev);
-  static int cus_of[16] = {0};
-  static bool attr_set[16] = {false};
-  if (!cus_of[dev]) {
-    int n = 256;
-    NH_CHECK_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
-    cus_of[dev] = n;
-  }
-  auto kern = k_p1hex_tri<MASS, COEF>;
-  if (!attr_set[dev]) {
-    NH_CHECK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p1r::LDS_BYTES));
-    attr_set[dev] = true;
-  }
-  p.nbj = (p.n1 + 1 + p1r::OW - 1) / p1r::OW;
-  p.nbk = (p.n2 + 1 + p1r::OW - 1) / p1r::OW;
-  NH_REQUIRE(a->max_workgroups >= 0, "nh_p1hex: negative max_workgroups");
-  const i64 units = (i64)p.nbj * p.nbk * (p.pl1 - p.pl0);
-  const unsigned grid = (unsigned)std::min<i64>(units, a->max_workgroups ? std::min(cus_of[dev], a->max_workgroups) : cus_of[dev]);
-  static const int delay = getenv("NH_P1HEX_TRI_DELAY") ? std::min(64, std::max(0, atoi(getenv("NH_P1HEX_TRI_DELAY")))) : 1;
-  p.wbnd = delay;  // (start delay of every second workgroup, in units of 4096 cycles)
-  static const int noprio = getenv("NH_P1HEX_TRI_NOPRIO") ? 1 : 0;
-  p.debug = noprio;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(768), p1r::LDS_BYTES, nh_stream(stream), p);
-  NH_LAUNCH_CHECK();
-  return NH_OK;
-}
-
-static int launch_tri(const nh_p1hex_args *a, P1Args &p, void *stream) {
-  const bool coef = p.qscale || p.qmass;
-  if (p.hasm) return coef ? launch_tri_inst<true, true>(a, p, stream) : launch_tri_inst<true, false>(a, p, stream);
-  return coef ? launch_tri_inst<false, true>(a, p, stream) : launch_tri_inst<false, false>(a, p, stream);
-}
-
-static int launch_tiles(const nh_p1hex_args *a, P1Args &p, void *stream) {
-  const bool coef = p.qscale || p.qmass;
-  if (p.hasm) return coef ? launch_tiles_inst<true, true>(a, p, stream) : launch_tiles_inst<true, false>(a, p, stream);
-  return coef ? launch_tiles_inst<false, true>(a, p, stream) : launch_tiles_inst<false, false>(a, p, stream);
 }
 
 template <bool VEC>
@@ -1202,12 +966,6 @@ int nh_p1hex_laplace(const nh_p1hex_args *a, void *stream) {
     if (Ke) NH_CHECK_HIP(hipFreeAsync(Ke, nh_stream(stream)));
     return NH_OK;
   }
-  // matrix kernel (read per launch: the tests compare the kernels within one process): skew (default) | tiles | march.  The exact-tile kernel
-  // (no lateral halo, tile faces exchanged between workgroups) is correct on every mesh of the test suite but measured SLOWER at 128^3 (0.21 ms
-  // against 0.167 ms: profiles/r04_c2_exact_tiles.md) and stays opt-in.
-  const char *env = getenv("NH_P1HEX_KERNEL");
-  if (env && !strcmp(env, "tiles")) return launch_tiles(a, p, stream);
-  if (env && !strcmp(env, "tri")) return launch_tri(a, p, stream);
   return launch_march<false>(a, p, stream);
 }
 

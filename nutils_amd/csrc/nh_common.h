@@ -196,5 +196,3 @@ int nh_fused_scalar(const nh_matrix_args *a, bool *done, hipStream_t s);
 void nh_fused_free(nh_fused_plan *f);
 // nh_owner.hip: the same for vector-valued blocks on small uniform bases (row tasks: Gram sums per scalar entry from D tables in LDS)
 int nh_owner_vector(const nh_matrix_args *a, const GSlots &slots, bool *done, hipStream_t s);
-// nh_assemble_p1hex.hip: exchange scratch of the exact-tile kernel
-int nh_p1hex_tiles_release(void);

@@ -837,7 +837,7 @@ extern "C" int nh_release_scratch(void) {
     g_scratch = nullptr, g_scratch_cap = 0;
   }
   NH_CHECK_HIP(hipDeviceSynchronize());
-  return nh_p1hex_tiles_release();
+  return NH_OK;
 }
 
 int nh_gather_prepare(nh_pattern *p, const nh_basis &test, const int32_t *elist, hipStream_t s) {

@@ -86,11 +86,7 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(USE0 ? 2
     for (int r = 0; r < R; ++r) {
       const int t = lane + 64 * r;
 #pragma unroll
-#ifdef NH_GS_NOLOAD  // (timing experiments: profiles/r06_c5_gram.md)
-      for (int i = 0; i < S; ++i) tt[r][i] = t < n ? 1. / (double)(t + i + 1) : 0.;
-#else
       for (int i = A0; i < S; ++i) tt[r][i] = t < n ? T[(i64)t * S + i] : 0.;
-#endif
     }
     if (live && lane < nq) {
       double det;
@@ -113,11 +109,7 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(USE0 ? 2
     if (lane == 0) meta[wave] = nb, kbl[wave] = kb;
     if (TRI) rkl[wave * 64 + lane] = rk;
     __builtin_amdgcn_wave_barrier();  // (a wave reads only the Jw rows / ranks it wrote itself: LDS operations of one wave execute in order)
-#ifdef NH_GS_NOSTAGE
-    const int n = tt[0][S - 1] == 1.2345e300 ? nb * nq : 0;
-#else
     const int n = nb * nq;
-#endif
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const int t = lane + 64 * r;
@@ -150,30 +142,6 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(USE0 ? 2
   int km0 = 0, kn0 = 0, knb = -1, kflags = 0;  // knb < 0: nothing to store
   auto flush = [&]() {
     if (knb < 0) return;
-#ifdef NH_GS_NOSTORE
-    if (K[0][0][0][0] != 1.2345e300) { knb = -1; return; }
-#endif
-#ifdef NH_GS_STORELIN  // (timing experiment: the same bytes, consecutive lanes on consecutive 16-byte words -- NOT the scratch layout)
-    if constexpr (NC == 2) {
-      double *lin = p.local + kbase - (i64)(kbase % 2);
-      int t = 0;
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          if (!((kflags >> (2 * i + j)) & 1)) continue;
-          const bool mir = km0 + i != kn0 + j;
-          *reinterpret_cast<double2 *>(lin + ((i64)(t++) * 64 * W + tid) * 2) = double2{K[i][j][0][0], K[i][j][0][1]};
-          *reinterpret_cast<double2 *>(lin + ((i64)(t++) * 64 * W + tid) * 2) = double2{K[i][j][1][0], K[i][j][1][1]};
-          if (mir) {
-            *reinterpret_cast<double2 *>(lin + ((i64)(t++) * 64 * W + tid) * 2) = double2{K[i][j][0][0], K[i][j][1][0]};
-            *reinterpret_cast<double2 *>(lin + ((i64)(t++) * 64 * W + tid) * 2) = double2{K[i][j][0][1], K[i][j][1][1]};
-          }
-        }
-      knb = -1;
-      return;
-    }
-#endif
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -217,55 +185,6 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(USE0 ? 2
       }
     knb = -1;
   };
-#ifdef NH_GS_NOPREFETCH
-  auto stage_direct = [&](i64 ib) {  // global memory -> LDS in one go, NH_GS_UNROLL table rounds in flight
-    ie = ib * E + wave;
-    live = wave < E && ib < nbatch && ie < p.nelems;
-    e = live ? (p.elist ? p.elist[ie] : ie) : 0;
-    nb = live ? bnb(p.test, e) : 0;
-    if (wave >= E) return;
-    double *D = Dall + wave * dsz, *Jw = Jall + wave * jsz;
-    if (live && lane < nq) {
-      double det;
-      geometry_at<ND>(p.geom, e, lane, nq, nullptr, gJ, det, nullptr);
-#pragma unroll
-      for (int j = 0; j < ND; ++j)
-#pragma unroll
-        for (int i = 0; i < ND; ++i) Jw[lane * JW + j * ND + i] = gJ[j][i];
-      Jw[lane * JW + ND * ND] = p.weights[lane] * fabs(det) * (p.scale ? p.scale[(p.emap_by_elem ? e : ie) * nq + lane] : 1.);
-    }
-    if (lane == 0) meta[wave] = nb, kbl[wave] = TRI ? p.tribase[e] : p.eoff ? p.eoff[e] : (p.emap_by_elem ? e : ie) * (i64)nb * nb;
-    if (TRI) rkl[wave * 64 + lane] = lane < nb ? p.trirank[boff(p.test, e) + lane] : 0;
-    __builtin_amdgcn_wave_barrier();
-    const double *T = p.test.T + bfn(p.test, e) * (i64)nq * S;
-    const int n = nb * nq;
-#pragma unroll NH_GS_UNROLL
-    for (int t = lane; t < n; t += 64) {
-      int m = (int)(((float)t + .5f) * rnq);
-      int q = t - m * nq;
-      if (q < 0) --m, q += nq;
-      if (q >= nq) ++m, q -= nq;
-      const double *Tt = T + (i64)t * S;
-      if (TRI) m = rkl[wave * 64 + m];
-      const double *Ji = Jw + q * JW;
-      double *dst = D + q * qs + m;
-      if (USE0) dst[0] = Tt[0];
-#pragma unroll
-      for (int i = 0; i < ND; ++i) {
-        double sm = 0;
-#pragma unroll
-        for (int j = 0; j < ND; ++j) sm += Tt[1 + j] * Ji[j * ND + i];
-        dst[(1 + i - A0) * mp] = sm;
-      }
-    }
-    if ((nb & 1) && lane < nq) {
-#pragma unroll
-      for (int a = A0; a < S; ++a) D[lane * qs + (a - A0) * mp + nb] = 0.;
-    }
-  };
-  stage_direct(blockIdx.x);
-  __syncthreads();
-#else
   eA = elem_id(blockIdx.x);
   elem_off(eA, oA0, oA1);
   eB = elem_id(blockIdx.x + gridDim.x);
@@ -273,7 +192,6 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(USE0 ? 2
   stage();
   __syncthreads();
   issue(blockIdx.x + gridDim.x);
-#endif
   for (i64 ib = blockIdx.x; ib < nbatch; ib += gridDim.x) {
     // ---- the 2 x 2 blocks of the E elements in LDS, dealt to the lanes (one block per lane: the launcher checks that they fit) ----
     int cnt[E + 1];
@@ -310,11 +228,7 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(USE0 ? 2
           for (int a = A0; a < S; ++a)
 #pragma unroll
             for (int b = A0; b < S; ++b) G[i][j][a][b] = 0.;
-#ifdef NH_GS_NOLOOP
-      for (int q = 0; q < 1; ++q) {
-#else
       for (int q = 0; q < nq; ++q) {
-#endif
         const double *Dq = Ds + q * qs;
         const double wq = Js[q * JW + ND * ND];
         double2 rm[S], rn[S];
@@ -355,14 +269,9 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(USE0 ? 2
         }
     }
     __syncthreads();  // every lane is done with the tables of this batch
-#ifdef NH_GS_NOPREFETCH  // (experiment: no table registers across the point loop -- fewer registers, more waves per SIMD, the load latency left to the other workgroups of the CU)
-    flush();
-    stage_direct(ib + gridDim.x);
-#else
     stage();          // the next batch's table (loaded during the point loop) to LDS
     issue(ib + 2 * gridDim.x);  // (loads BEFORE the stores: memory operations retire in order, loads queued behind 38 kB of stores would wait for their drain)
     flush();          // this batch's blocks to the scratch: they drain during the next point loop
-#endif
     __syncthreads();
   }
 }

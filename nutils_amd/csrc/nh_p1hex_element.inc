@@ -2,9 +2,9 @@
 // the element routine, and the reduction of the 36 upper-triangle entries (VEC: of the 8 values of K_e u_e) into the LDS rows of
 // the element's 8 vertices.  In scope: P1Args p; acc, slot_of; element (gi, gj, gk), its position (ej, ek) in the tile; constants VK,
 // NS, VW, VEC, MASS, COEF; macro NH_P1HEX_VERT(a, bb, c) = pointer to the staged data of local vertex (a, bb, c).
-#ifndef NH_P1HEX_X_PRELOADED
+// Declares X (vertex coordinates) and the macros NH_P1HEX_ELEM (global element index) and NH_P1HEX_SLOT (LDS address of an entry), the macros
+// for its own use only: both kernels that include it (k_p1hex_march, k_p1hex_skew) run it unchanged.
         double X[2][2][2][3];
-#endif
         double un[8];
 #pragma unroll
         for (int a = 0; a < 2; ++a)
@@ -12,20 +12,13 @@
           for (int bb = 0; bb < 2; ++bb)
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
-#ifndef NH_P1HEX_X_PRELOADED
               const double *src = NH_P1HEX_VERT(a, bb, c);
               X[a][bb][c][0] = src[0];
               X[a][bb][c][1] = src[1];
               X[a][bb][c][2] = src[2];
               un[a * 4 + bb * 2 + c] = VEC ? src[VW - 1] : 0.;
-#else
-              un[a * 4 + bb * 2 + c] = 0.;
-#endif
             }
-#ifndef NH_P1HEX_ELEM
 #define NH_P1HEX_ELEM (((i64)gi * p.n1 + gj) * p.n2 + gk)
-#define NH_P1HEX_ELEM_LOCAL
-#endif
         double qs[8];  // coefficient at the Gauss points (1 without a coefficient array)
 #pragma unroll
         for (int q = 0; q < 8; ++q) qs[q] = 1.;
@@ -45,11 +38,8 @@
 #pragma unroll
           for (int q = 0; q < 8; ++q) qm[q] = src[q];
         }
-#ifndef NH_P1HEX_SLOT
         double *const pl[2] = {acc + slot_of(gi) + (ej * VK + ek) * NS, acc + slot_of(gi + 1) + (ej * VK + ek) * NS};
 #define NH_P1HEX_SLOT(a0, a1, a2, b0, b1, b2) (pl[a0] + ((a1) * VK + (a2)) * NS + ((b0) - (a0)) * 9 + ((b1) - (a1)) * 3 + ((b2) - (a2)))
-#define NH_P1HEX_SLOT_LOCAL
-#endif
         if constexpr (VEC) {
           double r[8];
 #define NH_P1HEX_QS(q) qs[q]
@@ -86,9 +76,6 @@
 #pragma unroll
           for (int a = 0; a < 8; ++a) {
             const int a0 = a >> 2, a1 = (a >> 1) & 1, a2 = a & 1;
-#ifdef NH_P1HEX_LATE_HOOK
-            if (a == 3) { NH_P1HEX_LATE_HOOK }  // (between the LDS atomics of two rows: the compiler keeps it there)
-#endif
 #pragma unroll
             for (int bb = a; bb < 8; ++bb) {
               const int b0 = bb >> 2, b1 = (bb >> 1) & 1, b2 = bb & 1;
@@ -100,11 +87,5 @@
           }
         }
         }  // !VEC
-#ifdef NH_P1HEX_ELEM_LOCAL
 #undef NH_P1HEX_ELEM
-#undef NH_P1HEX_ELEM_LOCAL
-#endif
-#ifdef NH_P1HEX_SLOT_LOCAL
 #undef NH_P1HEX_SLOT
-#undef NH_P1HEX_SLOT_LOCAL
-#endif

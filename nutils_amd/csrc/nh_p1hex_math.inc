@@ -1,5 +1,6 @@
 // Element math of the P1-hex Laplace fast path, textually included into each kernel that needs it (a function taking the kernel
-// argument struct by reference makes hipcc 7.2 copy it to private memory and costs 36 VGPRs + scratch in the main kernel).
+// argument struct by reference makes hipcc 7.2 copy it to private memory and costs 36 VGPRs + scratch in the main kernel).  Straight-line
+// code without hooks or switches: nh_p1hex_element.inc, k_p1hex_unit_matrix, nh_gather.hip and tools/ubench/p1hex_math.hip include it as it is.
 // In scope at the include site: P1Args p; macros NH_P1HEX_QS(q), NH_P1HEX_QM(q) (diffusion / mass coefficient at Gauss point q, or 1.);
 // bool hasm (uniform: mass term requested) and output double Mm[3][3][3] (mass term by pair classes); double X[2][2][2][3]; outputs double R0[3][3], R1[3][3], R2[3][3] (diagonal j == k
 // terms, indexed by the pair classes p_d = a_d + b_d) and W01[2][2][3], W02[2][2][3], W12[2][2][3] (off-diagonal terms).
@@ -69,11 +70,7 @@
         A[2][1] = c0[2] * c1[0] - c0[0] * c1[2];
         A[2][2] = c0[0] * c1[1] - c0[1] * c1[0];
         const double det = c0[0] * A[0][0] + c0[1] * A[0][1] + c0[2] * A[0][2];
-#ifdef NH_P1HEX_SC  // (the exact-tile kernel runs the routine for all lanes, elements outside the mesh with a zero factor)
-        const double sc = NH_P1HEX_SC(p.wk[qa][qb][qc] * NH_P1HEX_QS(qa * 4 + qb * 2 + qc) * fast_rcp(fabs(det)));
-#else
         const double sc = p.wk[qa][qb][qc] * NH_P1HEX_QS(qa * 4 + qb * 2 + qc) * fast_rcp(fabs(det));
-#endif
         const double m00 = sc * (A[0][0] * A[0][0] + A[0][1] * A[0][1] + A[0][2] * A[0][2]);
         const double m11 = sc * (A[1][0] * A[1][0] + A[1][1] * A[1][1] + A[1][2] * A[1][2]);
         const double m22 = sc * (A[2][0] * A[2][0] + A[2][1] * A[2][1] + A[2][2] * A[2][2]);
@@ -83,15 +80,8 @@
         D0[qb][qc] = qa ? D0[qb][qc] + m00 : m00;
         D1[qa][qc] = qb ? D1[qa][qc] + m11 : m11;
         D2[qa][qb] = qc ? D2[qa][qb] + m22 : m22;
-#ifdef NH_P1HEX_SC
-        if (hasm) Dm[qa][qb][qc] = NH_P1HEX_SC(p.wm[qa][qb][qc] * NH_P1HEX_QM(qa * 4 + qb * 2 + qc) * fabs(det));
-#else
         if (hasm) Dm[qa][qb][qc] = p.wm[qa][qb][qc] * NH_P1HEX_QM(qa * 4 + qb * 2 + qc) * fabs(det);
-#endif
       }
-#ifdef NH_P1HEX_MID_HOOK
-  NH_P1HEX_MID_HOOK
-#endif
   // ---- axis-by-axis contractions -------------------------------------------------------------------
   {
     double U[2][3];

@@ -460,9 +460,8 @@ def test_first_touch_coloured_assembly(case, monkeypatch):
 
 
 def test_p1hex_skewed_vs_marching_kernel(monkeypatch):
-    '''The four matrix kernels -- role-skewed halo tiles (skew), two arithmetic waves + one memory wave per SIMD (tri), exact tiles with inter-workgroup
-    face exchange (tiles), marching halo tiles (march) -- on random shapes, layer / plane ranges and workgroup limits: the same set of entries is written (the
-    value array is handed over full of NaN), values agree to rounding.  Shapes reach several 16 x 16 tiles per axis, partial last tiles,
+    '''The two matrix kernels -- role-skewed halo tiles (skew), marching halo tiles (march) -- on random shapes, layer / plane ranges and workgroup
+    limits: the same set of entries is written (the value array is handed over full of NaN), values agree to rounding.  Shapes reach several 16 x 16 tiles per axis, partial last tiles,
     single-line tiles and more units than workgroups (several runs per workgroup).'''
     from nutils_amd import kernels, device, points
     x1, w1 = points.gauss1(2)
@@ -485,24 +484,23 @@ def test_p1hex_skewed_vs_marching_kernel(monkeypatch):
         verts = device.to_dev(g, 'float64')
         rowptr, colidx = kernels.p1hex_pattern(shape)
         got = []
-        for kern in ('tiles', 'tri', 'skew', 'march'):
+        for kern in ('skew', 'march'):
             monkeypatch.setenv('NH_P1HEX_KERNEL', kern)
             values = device.empty(colidx.numel(), 'float64')
             values.fill_(float('nan'))
             kernels.p1hex_laplace(shape=shape, values=values, gauss_x=x1, gauss_w=w1, verts=verts, layers=(l0, l1), planes=(p0, p1), max_workgroups=(it % 3) * 100 if it != 19 else 7)
             got.append(device.to_host(values))
-        written = ~numpy.isnan(got[3])
+        written = ~numpy.isnan(got[1])
         assert written.any()
-        for k in (0, 1, 2):
-            assert numpy.array_equal(~numpy.isnan(got[k]), written), (shape, k)
-            assert numpy.abs(got[k][written] - got[3][written]).max() <= 1e-14 * numpy.abs(got[3][written]).max(), (shape, k)
+        assert numpy.array_equal(~numpy.isnan(got[0]), written), shape
+        assert numpy.abs(got[0][written] - got[1][written]).max() <= 1e-14 * numpy.abs(got[1][written]).max(), shape
 
 
-def test_p1hex_tiles_repeated_launches_and_layout_changes(monkeypatch):
-    '''The exact-tile kernel (NH_P1HEX_KERNEL=tiles) keeps flags across launches (epoch) and re-lays its exchange scratch when the mesh changes:
-    alternate two meshes, several launches each, every result equal to the first of its mesh and free of NaN.'''
+def test_p1hex_repeated_launches_alternating_meshes(monkeypatch):
+    '''The default matrix kernel remembers per-device launch state (CU count, LDS attribute) across launches and must not depend on the mesh of the
+    previous one: alternate two meshes, several launches each, every result equal to the first of its mesh and free of NaN.'''
     from nutils_amd import kernels, device, points
-    monkeypatch.setenv('NH_P1HEX_KERNEL', 'tiles')
+    monkeypatch.delenv('NH_P1HEX_KERNEL', raising=False)
     x1, w1 = points.gauss1(2)
     first = {}
     for it in range(8):
