@@ -696,6 +696,11 @@ int nh_csr_compact(int64_t nnz, int64_t ncols, const int64_t *colidx_dev, int32_
 int nh_csr_spmv(const nh_csr *A, double alpha, const double *x_dev, double beta, const double *b_dev, const unsigned char *rowmask_dev, double *y_dev, void *stream);
 /* diag[i] = A_ii, 0 for a row without a diagonal entry (Matrix.diagonal) */
 int nh_csr_diagonal(const nh_csr *A, double *diag_dev, void *stream);
+/* The support of A above a tolerance (Matrix.rowsupp, matrix/_base.py): rowsupp[i] = 1 when row i holds an entry with |a| > tol (strictly; tol >= 0), else 0;
+ * colsupp[j] likewise for column j.  uint8 [nrows] and [ncols]; either may be NULL.  The entry point zero-fills what it is given; a matrix without entries
+ * is no launch.  Column indices int32 or int64 as for the product, and its rows-to-lanes mapping.  Several lanes may store the byte 1 to one address: plain
+ * byte stores, no atomics, and the result, a set, is the same at every call. */
+int nh_csr_support(const nh_csr *A, double tol, unsigned char *rowsupp_dev, unsigned char *colsupp_dev, void *stream);
 /* Preconditioned conjugate gradients for square A, symmetric positive definite on the rows / columns the mask keeps, entirely on the
  * device: an iteration is three launches -- q = mask(A p) with partial sums of p . q per workgroup; alpha from the partials (summed by
  * every workgroup in the same order), x += alpha p, r -= alpha q, partials of r . z and r . r with z = dinv r; beta from those and

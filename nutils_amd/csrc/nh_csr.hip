@@ -10,6 +10,10 @@
 //     DOT = 1: additionally the workgroup's share of x . y goes to partial[blockIdx.x] (the p . Ap of a CG step).
 //     DOT = 2: the shares of w . y and y . y, w a vector of its own, go to partial[blockIdx.x] and partial2[blockIdx.x] (the two products of a BiCGStab
 //     step); the kernel does nothing at all when *skip != 0 (the iteration has stopped).
+//   * k_csr_support<L, Idx>: the support of the matrix above a tolerance, by the product's mapping (L lanes per row, a wave reads one contiguous span):
+//     a lane that meets |a| > tol stores the byte 1 to colsupp[col] and remembers it for the row, whose L lanes are folded with __shfl_xor before lane 0
+//     stores rowsupp[row].  Lanes that meet the same column store the same byte to the same address: plain vector byte stores, nothing atomic, and since
+//     the result is a set it does not depend on who comes first.  The arrays are zeroed before the launch.
 //   * k_cg_update / k_cg_direction: the vector half of a CG step.  Every workgroup sums the partials of the kernel before it in the
 //     same order and so holds the same alpha / beta; scalars that cross an iteration live in two cells each, one written and one read
 //     per kernel, so no kernel reads a cell that one of its own workgroups writes.
@@ -87,6 +91,29 @@ __global__ __launch_bounds__(WG) void k_csr_spmv(i64 nrows, const i64 *__restric
       partial[blockIdx.x] = dot;
       if (DOT == 2) partial2[blockIdx.x] = dot2;
     }
+  }
+}
+
+template <int L, class Idx>
+__global__ __launch_bounds__(WG) void k_csr_support(i64 nrows, const i64 *__restrict__ rowptr, const Idx *__restrict__ col, const double *__restrict__ values, double tol,
+                                                    unsigned char *__restrict__ rowsupp, unsigned char *__restrict__ colsupp) {
+  constexpr int G = WG / L;
+  const int lane = threadIdx.x & (L - 1);
+  for (i64 base = (i64)blockIdx.x * G; base < nrows; base += (i64)gridDim.x * G) {  // (uniform trip count: every lane takes part in the shuffles)
+    const i64 row = base + threadIdx.x / L;
+    const bool live = row < nrows;
+    int any = 0;
+    if (live) {
+      const i64 k1 = rowptr[row + 1];
+      for (i64 k = rowptr[row] + lane; k < k1; k += L)
+        if (fabs(values[k]) > tol) {  // (strict; false for NaN)
+          any = 1;
+          if (colsupp) colsupp[col[k]] = 1;
+        }
+    }
+#pragma unroll
+    for (int o = L >> 1; o; o >>= 1) any |= __shfl_xor(any, o, L);
+    if (rowsupp && live && lane == 0 && any) rowsupp[row] = 1;
   }
 }
 
@@ -442,6 +469,26 @@ int spmv(const nh_csr *A, double alpha, const double *x, double beta, const doub
   return NH_OK;
 }
 
+template <class Idx>
+void launch_support(int L, const nh_csr *A, const Idx *col, double tol, unsigned char *rowsupp, unsigned char *colsupp, hipStream_t s) {
+#define NH_SUPPORT(LL)                                                                                                                                            \
+  case LL:                                                                                                                                                        \
+    hipLaunchKernelGGL((k_csr_support<LL, Idx>), dim3(spmv_grid(A->nrows, LL)), dim3(WG), 0, s, (i64)A->nrows, (const i64 *)A->rowptr_dev, col, A->values_dev, tol, rowsupp, \
+                       colsupp);                                                                                                                                  \
+    break;
+  switch (L) {
+    NH_SUPPORT(1)
+    NH_SUPPORT(2)
+    NH_SUPPORT(4)
+    NH_SUPPORT(8)
+    NH_SUPPORT(16)
+    NH_SUPPORT(32)
+    default:
+    NH_SUPPORT(64)
+  }
+#undef NH_SUPPORT
+}
+
 }  // namespace
 
 extern "C" {
@@ -491,6 +538,22 @@ int nh_csr_diagonal(const nh_csr *A, double *diag_dev, void *stream) {
     hipLaunchKernelGGL(k_csr_diagonal<int32_t>, grid, dim3(WG), 0, nh_stream(stream), (i64)A->nrows, (const i64 *)A->rowptr_dev, A->col32_dev, A->values_dev, diag_dev);
   else
     hipLaunchKernelGGL(k_csr_diagonal<i64>, grid, dim3(WG), 0, nh_stream(stream), (i64)A->nrows, (const i64 *)A->rowptr_dev, (const i64 *)A->colidx_dev, A->values_dev, diag_dev);
+  NH_LAUNCH_CHECK();
+  return NH_OK;
+}
+
+int nh_csr_support(const nh_csr *A, double tol, unsigned char *rowsupp_dev, unsigned char *colsupp_dev, void *stream) {
+  if (int rc = check_csr("nh_csr_support", A)) return rc;
+  NH_REQUIRE(tol >= 0., "nh_csr_support: the tolerance must not be negative");
+  hipStream_t s = nh_stream(stream);
+  if (rowsupp_dev && A->nrows) NH_CHECK_HIP(hipMemsetAsync(rowsupp_dev, 0, (size_t)A->nrows, s));
+  if (colsupp_dev && A->ncols) NH_CHECK_HIP(hipMemsetAsync(colsupp_dev, 0, (size_t)A->ncols, s));
+  if (!A->nrows || !A->nnz || !(rowsupp_dev || colsupp_dev)) return NH_OK;  // an empty matrix has an empty support: no launch
+  const int L = A->lanes ? A->lanes : nh_csr_lanes(A->nrows, A->nnz);
+  if (A->col32_dev)
+    launch_support(L, A, A->col32_dev, tol, rowsupp_dev, colsupp_dev, s);
+  else
+    launch_support(L, A, (const i64 *)A->colidx_dev, tol, rowsupp_dev, colsupp_dev, s);
   NH_LAUNCH_CHECK();
   return NH_OK;
 }

@@ -848,6 +848,14 @@ def csr_diagonal(values, rowptr, colidx, ncols, *, col32=None):
     return diag
 
 
+def csr_support(values, rowptr, colidx, ncols, tol=0., *, rows=True, cols=True, col32=None, lanes=0):
+    '''(rowsupp, colsupp): uint8 device vectors, 1 where a row / a column holds an entry with |a| > tol (nh_csr_support); None for the one not asked for'''
+    rowsupp = device.empty(rowptr.numel() - 1, 'uint8') if rows else None
+    colsupp = device.empty(int(ncols), 'uint8') if cols else None
+    _lib.call('nh_csr_support', ctypes.byref(_csr(values, rowptr, colidx, ncols, col32, lanes)), float(tol), device.ptr(rowsupp), device.ptr(colsupp), device.stream())
+    return rowsupp, colsupp
+
+
 def cg_work():
     '''the work array of a CG solve (nh_cg_work_doubles): [0] = r . r of the recurrence, [1] = breakdown flag, [2] = the bound of `cg_stop`'''
     return device.empty(_lib.load().nh_cg_work_doubles(), 'float64')

@@ -12,7 +12,8 @@ triplet in HBM as a ``HipMatrix``: products, the diagonal and two Jacobi-
 preconditioned Krylov solves -- conjugate gradients ('cg') for symmetric
 positive definite systems, BiCGStab ('bicgstab') for any square matrix --
 run on the device (nh_csr.hip); ``function.eval(function.as_matrix(K))`` builds
-one without the triplet ever visiting the host.  What a ``HipMatrix`` does
+one without the triplet ever visiting the host, and so does ``solver.System``
+under this backend (``assemble_device``).  What a ``HipMatrix`` does
 through scipy and a re-upload -- ``submatrix``, ``T``, every solver other than
 'cg' and 'bicgstab', sums of matrices with different patterns -- says so in its
 docstring.
@@ -167,7 +168,7 @@ class HipMatrix:
     first use on the device.  The matrix keeps references and never writes into them.  At the first product the column indices are narrowed to int32 once
     (12 instead of 16 bytes per entry; matrices with more than 2^31 - 1 columns keep the int64 indices).
 
-    On the device: products (nh_csr_spmv), the diagonal, scalar multiples, sums of matrices that share their index tensors, `solve(solver='cg')`, a
+    On the device: products (nh_csr_spmv), the diagonal, `rowsupp` / `colsupp` (nh_csr_support), scalar multiples, sums of matrices that share their index tensors, `solve(solver='cg')`, a
     Jacobi-preconditioned conjugate-gradient iteration for SYMMETRIC POSITIVE DEFINITE systems, and `solve(solver='bicgstab')`, a Jacobi-preconditioned
     BiCGStab iteration for ANY square system (nonsymmetric, indefinite); both with ONE right-hand side.  `iterations` is the iteration count of the last device
     solve.  Through scipy and PCIe (export, host operation, re-upload): `submatrix`, `T`, sums of matrices with different patterns, every other solver.'''
@@ -249,6 +250,23 @@ class HipMatrix:
         '''A_ii as a host vector, 0 where a row has no diagonal entry (Matrix.diagonal)'''
         from . import device
         return device.to_host(self._diagonal_dev())
+
+    def _support(self, tol, rows):
+        from . import device, kernels
+        tol = float(tol)
+        if not tol >= 0:
+            raise MatrixError(f'the tolerance of a support must not be negative, got {tol}')
+        values, rowptr, colidx = self.triplet()
+        supp = kernels.csr_support(values, rowptr, colidx, self._ncols, tol, rows=rows, cols=not rows, col32=self._columns(), lanes=self.lanes)[0 if rows else 1]
+        return device.to_host(supp).astype(bool)
+
+    def rowsupp(self, tol=0):
+        '''host bool vector: the rows that hold an entry with |a| > tol (Matrix.rowsupp, matrix/_base.py:92-98), found on the device (nh_csr_support)'''
+        return self._support(tol, True)
+
+    def colsupp(self, tol=0):
+        '''host bool vector: the columns that hold an entry with |a| > tol (nh_csr_support); what `System.solve_constraints` asks of its matrix'''
+        return self._support(tol, False)
 
     # -- host side (PCIe)
 
@@ -471,6 +489,12 @@ class _HipBackend:
         return HipMatrix(values, rowptr, colidx, ncols, validate=False)  # (`assemble_csr` has checked the triplet)
 
     assemble_trusted = assemble
+
+    @staticmethod
+    def assemble_device(values_dev, rowptr_dev, colidx_dev, ncols):
+        '''The device hand-over: a matrix on the tensors the assembly left in HBM, nothing copied.  `solver.System` looks for this attribute; a backend
+        that has it receives device tensors and solves where they lie.'''
+        return HipMatrix(values_dev, rowptr_dev, colidx_dev, ncols)
 
 
 class _Backend:

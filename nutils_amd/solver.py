@@ -6,7 +6,12 @@ arguments, merges the blocks (``matrix.assemble_block_csr``, matrix/__init__.py:
 applies constraints on the host (NaN = free dof, solver.py:273-315) and hands the
 matrix to the host solver (scipy).  Linear systems are solved directly, nonlinear ones
 (field-dependent coefficient functions) by plain Newton iteration (solver.py Newton
-without line search); minimisation / pseudo-time drivers stay with the reference.'''
+without line search); minimisation / pseudo-time drivers stay with the reference.
+
+Under a matrix backend with a device hand-over (``assemble_device``: ``matrix.backend('hip')``)
+the merged Jacobian stays in HBM instead: it is a ``HipMatrix`` on the plan's index tensors,
+constraints are the row mask of its Krylov solve, and `linargs` (solver name, tolerance) go to
+every linear solve.  Residual, iterate and arguments remain host vectors.'''
 
 import numpy
 
@@ -109,6 +114,8 @@ class System:
                                  for row in self.block_jacobian for blk in row for _, itg, _ in blk.terms)
         self.is_constant_matrix = not any(_field_dependent(itg) for row in self.block_jacobian for blk in row for _, itg, _ in blk.terms)
         self._jac = None
+        self._device_jac = None  # (backend, the last Jacobian it made of device tensors)
+        self.linear_iterations = []  # `jac.iterations` of every linear solve of the last solve / solve_constraints (None where a matrix counts none)
 
     # -- assembly (solver.py:318-386) --
 
@@ -117,9 +124,12 @@ class System:
         group of matrix terms is one device assembly; the position of each of its CSR entries in the merged block matrix is
         precomputed.  The groups without a coefficient function are assembled here, once, into `_base`; the others (the
         field-dependent blocks) are re-assembled per step into the compact array of the entries they touch (`_dynpos`), which is
-        all that crosses PCIe afterwards (`_HostMirror`).  Replaces the per-row Python loop of matrix.assemble_block_csr
-        (matrix/__init__.py:141-147) on the per-step path.'''
+        all that crosses PCIe afterwards on the host route (`_HostMirror`).  Replaces the per-row Python loop of
+        matrix.assemble_block_csr (matrix/__init__.py:141-147) on the per-step path.  The index arithmetic (sorted unique keys
+        row * size + column, binary searches) runs where the groups' index tensors lie: the merged pattern is left in HBM
+        (`_merged_rowptr_dev`, `_merged_colidx_dev`) for the device route, and the host route fetches its copy at the first use.'''
         from . import device, kernels
+        t = device.torch()
         groups, keys = [], []
         for i, row in enumerate(self.block_jacobian):
             for j, blk in enumerate(row):
@@ -129,35 +139,43 @@ class System:
                 for terms in by_sample.values():
                     plan = _sample._MatrixPlan(terms)
                     values, rowptr, colidx, ncols = plan.run(arguments)
-                    rp, ci = device.to_host(rowptr), device.to_host(colidx)
-                    rows = numpy.repeat(numpy.arange(len(rp) - 1, dtype=numpy.int64), numpy.diff(rp)) + int(self.offsets[i])
-                    key = rows * self.size + ci + int(self.offsets[j])
+                    rows = t.repeat_interleave(t.arange(rowptr.numel() - 1, device=rowptr.device), rowptr[1:] - rowptr[:-1]) + int(self.offsets[i])
                     constant = not any(_field_dependent(itg) for _, itg, _ in terms)
-                    groups.append(dict(plan=plan, constant=constant, values=values if constant else None, n=len(key)))
-                    keys.append(key)
-        allkeys = numpy.concatenate(keys) if keys else numpy.zeros(0, dtype=numpy.int64)
-        ukeys = numpy.unique(allkeys)
-        rows, cols = numpy.divmod(ukeys, self.size)
-        self._merged_rowptr = numpy.searchsorted(rows, numpy.arange(self.size + 1)).astype(numpy.int64)
-        self._merged_colidx = cols.astype(numpy.int64)
-        slots = [numpy.searchsorted(ukeys, key) for key in keys]
+                    groups.append(dict(plan=plan, constant=constant, values=values if constant else None, n=colidx.numel()))
+                    keys.append(rows * self.size + colidx + int(self.offsets[j]))
+        ukeys = t.unique(t.cat(keys))  # (sorted)
+        rows = t.div(ukeys, self.size, rounding_mode='floor')
+        self._merged_rowptr_dev = t.searchsorted(rows, t.arange(self.size + 1, device=rows.device))
+        self._merged_colidx_dev = ukeys - rows * self.size
+        slots = [t.searchsorted(ukeys, key) for key in keys]
         dyn = [slot for grp, slot in zip(groups, slots) if not grp['constant']]
-        self._dynpos = numpy.unique(numpy.concatenate(dyn)) if dyn else numpy.zeros(0, dtype=numpy.int64)
-        self._dynpos_dev = device.to_dev(self._dynpos, 'int64')
-        self._base = device.zeros(len(ukeys), 'float64')
+        self._dynpos_dev = t.unique(t.cat(dyn)) if dyn else device.zeros(0, 'int64')
+        ndyn = self._dynpos_dev.numel()
+        self._base = device.zeros(ukeys.numel(), 'float64')
         for grp, slot in zip(groups, slots):
             if grp['constant']:
-                kernels.monomial(grp.pop('values'), [], [], self._base, out_index=device.to_dev(slot, 'int64'))
+                kernels.monomial(grp.pop('values'), [], [], self._base, out_index=slot)
             else:
-                dslot = numpy.searchsorted(self._dynpos, slot)
-                grp['dslot'] = device.to_dev(dslot, 'int64')
+                dslot = grp['dslot'] = t.searchsorted(self._dynpos_dev, slot)
                 # the group's entries ARE the dynamic entries, in the same order (one field-dependent block on one sample, Cahn-Hilliard): it is assembled
                 # straight into the compact array (no array of its own, no pass that adds it)
-                grp['direct'] = len(dslot) == len(self._dynpos) and bool((dslot == numpy.arange(len(dslot))).all())
-        self._dyn_base = device.empty(len(self._dynpos), 'float64')
+                grp['direct'] = dslot.numel() == ndyn and bool((dslot == t.arange(ndyn, device=dslot.device)).all())
+        self._dyn_base = device.empty(ndyn, 'float64')
         kernels.index_copy(self._base, self._dyn_base, src_index=self._dynpos_dev)
         self._groups = [grp for grp in groups if not grp['constant']]
         self._mirror = None
+        self._plan_host = {}
+
+    def _on_host(self, name):
+        '''an index array of the merge plan as a host array, fetched once (the host route, `assemble_jacobian_free`)'''
+        from . import device
+        if name not in self._plan_host:
+            self._plan_host[name] = device.to_host(getattr(self, name + '_dev'))
+        return self._plan_host[name]
+
+    _merged_rowptr = property(lambda self: self._on_host('_merged_rowptr'))
+    _merged_colidx = property(lambda self: self._on_host('_merged_colidx'))
+    _dynpos = property(lambda self: self._on_host('_dynpos'))
 
     def _dyn_values(self, arguments):
         '''Values of the merged Jacobian at `_dynpos` (the entries that field-dependent blocks contribute to), on the device.'''
@@ -174,7 +192,7 @@ class System:
         '''Values of the merged block Jacobian on the device (pattern: _merged_rowptr, _merged_colidx).'''
         from . import kernels
         merged = self._base.clone()
-        if len(self._dynpos):
+        if self._dynpos_dev.numel():
             kernels.index_copy(self._dyn_values(arguments), merged, dst_index=self._dynpos_dev)
         return merged
 
@@ -184,6 +202,31 @@ class System:
         matrix wraps the page-locked array the device writes into; it is overwritten by the assembly after the next one (two arrays
         alternate), which is all a Newton driver needs and saves a host copy of the values (C4: 0.2 GB).'''
         return self._finish_jacobian(self._start_jacobian(arguments, None), copy)
+
+    @staticmethod
+    def _device_backend():
+        '''the current matrix backend if it takes device tensors (`assemble_device`), else None: the host route'''
+        backend = _matrix.backend.current
+        return backend if hasattr(backend, 'assemble_device') else None
+
+    def _start_jacobian_device(self, backend, arguments, enqueued=None):
+        '''`_start_jacobian` on the device route: the matrix is made of `_merged_values(arguments)` (fresh per call) and the plan's index tensors where they
+        lie; a later one shares the index tensors and their narrowed copy with the one before it (`HipMatrix._with_values`); a constant matrix is made once.'''
+        last = self._device_jac[1] if self._device_jac is not None and self._device_jac[0] is backend else None
+        if last is not None and self.is_constant_matrix:
+            return lambda copy=False: last
+        if not hasattr(self, '_groups'):
+            self._build_merge_plan(arguments)
+        values = self._merged_values(arguments)
+        if enqueued:
+            enqueued()
+        if hasattr(last, '_with_values'):
+            last._columns()  # (made by the first matrix that multiplies, handed on from there)
+            jac = last._with_values(values)
+        else:
+            jac = backend.assemble_device(values, self._merged_rowptr_dev, self._merged_colidx_dev, self.size)
+        self._device_jac = backend, jac
+        return lambda copy=False: jac
 
     def assemble_jacobian_free(self, arguments, free, copy=True):
         '''jac.submatrix(free, free) of the reference (solver.py:332,386) WITHOUT the host-side slicing: the positions of the free-free
@@ -206,6 +249,9 @@ class System:
         changed entries travel to the host on a side stream; `assemble_jacobian_residual` puts the residual of the step there.
         `enqueued`: called once the assembly kernels are enqueued, before the copy to the host is.'''
         from . import device, kernels
+        backend = self._device_backend() if free is None else None
+        if backend is not None:
+            return self._start_jacobian_device(backend, arguments, enqueued)
         if free is None and self._jac is not None and self.is_constant_matrix:
             return lambda copy=False: self._jac
         if not hasattr(self, '_groups'):
@@ -378,13 +424,29 @@ class System:
 
     # -- solves --
 
-    def solve(self, *, arguments=None, constrain=None, tol=0., maxiter=25):
-        '''Direct (linear) or Newton (nonlinear) solve; `constrain[trial]` holds NaN for free dofs (solver.py:440-500).'''
+    def _linear_solve(self, jac, res, linargs, lenient=False, **kwargs):
+        if linargs is None:
+            dx = jac.solve(res, **kwargs)
+        else:
+            dx = (getattr(jac, 'solve_leniently', jac.solve) if lenient else jac.solve)(res, **kwargs, **linargs)
+        self.linear_iterations.append(getattr(jac, 'iterations', None))
+        return dx
+
+    def solve(self, *, arguments=None, constrain=None, tol=0., maxiter=25, linargs=None):
+        '''Direct (linear) or Newton (nonlinear) solve; `constrain[trial]` holds NaN for free dofs (solver.py:440-500).  `linargs`: keyword arguments of
+        every linear solve (solver.py:618-661): a linear system calls `jac.solve(res, **linargs)`, a Newton step `jac.solve_leniently(res, **linargs)` with
+        rtol = 1e-3 unless `linargs` names a tolerance.  Under a matrix backend that takes device tensors (`matrix.backend('hip')`) the Jacobian stays in HBM
+        and the constraints are the row mask of its solve; that solve is iterative, so `linargs` must name a `solver` and a tolerance.'''
         x, free = self._pack(dict(arguments or {}), constrain)
         args = self._unpack(dict(arguments or {}), x)
         if not self.is_linear and tol <= 0:
             raise ValueError('iterative solver requires a strictly positive tolerance')
-        sub = None if free.all() else free  # constraint elimination on the device: only the free-free block travels to the host solver
+        if linargs is not None and not self.is_linear and 'atol' not in linargs and 'rtol' not in linargs:
+            linargs = dict(linargs, rtol=1e-3)
+        on_device = self._device_backend() is not None
+        # host route: constraint elimination on the device, only the free-free block travels to the host solver; device route: the whole matrix stays, with a row mask
+        sub = None if on_device or free.all() else free
+        self.linear_iterations = []
         for it in range(maxiter + 1):
             if self.is_linear:
                 res, jac = self.assemble_residual(args), None
@@ -399,15 +461,17 @@ class System:
                 raise SolverError(f'failed to converge in {maxiter} iterations (residual norm {resnorm:.1e})')
             if jac is None:
                 jac = self._start_jacobian(args, sub)()  # (zero-copy: used before the next assembly)
-            if sub is None:
-                x = x - jac.solve(res)
+            if on_device:
+                x = x - self._linear_solve(jac, res, linargs, not self.is_linear, constrain=~free)
+            elif sub is None:
+                x = x - self._linear_solve(jac, res, linargs, not self.is_linear)
             else:
-                x[free] -= jac.solve(res[free])
+                x[free] -= self._linear_solve(jac, res[free], linargs, not self.is_linear)
             args = self._unpack(args, x)
         return args
 
     def step(self, *, arguments, suffix, timestep=None, timesteparg=None, **solveargs):
-        '''Advance a time step (solver.py:503-560): copies trial arguments to name+suffix, then solves.'''
+        '''Advance a time step (solver.py:503-560): copies trial arguments to name+suffix, then solves (`solveargs`: the keywords of `solve`, `linargs` among them).'''
         arguments = dict(arguments)
         for t in self.trials:
             if t in arguments:
@@ -416,19 +480,24 @@ class System:
             arguments[timesteparg] = timestep
         return self.solve(arguments=arguments, **solveargs)
 
-    def solve_constraints(self, *, droptol, arguments=None, constrain=None):
+    def solve_constraints(self, *, droptol, arguments=None, constrain=None, linargs=None):
         '''Dirichlet constraints by boundary projection (solver.py:562-612): solve on the dofs whose matrix column has an
-        entry above droptol, return NaN for all others.'''
+        entry above droptol, return NaN for all others.  `linargs`: keyword arguments of the linear solve.  A matrix that knows its
+        own support (`HipMatrix.colsupp`, on the device) is asked for it instead of being exported.'''
         if not self.is_linear:
             raise ValueError('system is not linear')
         x, free = self._pack(dict(arguments or {}), constrain)
         args = self._unpack(dict(arguments or {}), x)
         jac, res = self.assemble_jacobian_residual(args)
-        data, colidx, _ = jac.export('csr')
-        mycons = numpy.ones(self.size, dtype=bool)
-        mycons[colidx[abs(data) > droptol]] = False
+        if hasattr(jac, 'colsupp'):
+            mycons = ~jac.colsupp(droptol)
+        else:
+            data, colidx, _ = jac.export('csr')
+            mycons = numpy.ones(self.size, dtype=bool)
+            mycons[colidx[abs(data) > droptol]] = False
         mycons |= ~free
-        dx = -jac.solve(res, constrain=mycons)
+        self.linear_iterations = []
+        dx = -self._linear_solve(jac, res, linargs, constrain=mycons)
         x = x + dx
         x[mycons & free] = numpy.nan
         out = dict(constrain or {})
