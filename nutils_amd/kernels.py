@@ -600,6 +600,8 @@ def p2hex_matrix(*, values, **kwargs):
 
 def monomial_csr(rowptr, colidx, values, x, y, alpha=1.):
     '''y[r] += alpha * sum_k values[k] x[colidx[k]] (nh_monomial_csr).'''
+    if rowptr.numel() <= 1:  # (no rows: nothing to add to; tensors without elements have no allocation and the C ABI refuses their NULL pointers)
+        return
     _lib.call('nh_monomial_csr', rowptr.numel() - 1, device.ptr(rowptr), device.ptr(colidx), device.ptr(values), device.ptr(x), float(alpha), device.ptr(y),
               device.stream())
 
@@ -607,6 +609,8 @@ def monomial_csr(rowptr, colidx, values, x, y, alpha=1.):
 def monomial(values, args, indices, out, out_index=None, alpha=1.):
     '''out[out_index[i]] += alpha values[i] prod_k args[k][indices[k][i]] (nh_monomial).'''
     n = len(args)
+    if not values.numel():  # (no entries: as in monomial_csr)
+        return
     A = (ctypes.c_void_p * max(n, 1))(*[a.data_ptr() for a in args])
     I = (ctypes.c_void_p * max(n, 1))(*[i.data_ptr() for i in indices])
     _lib.call('nh_monomial', values.numel(), device.ptr(values), n, A, I, device.ptr(out_index), float(alpha), device.ptr(out), device.stream())
