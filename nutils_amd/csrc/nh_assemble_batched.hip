@@ -643,7 +643,8 @@ __global__ __launch_bounds__(NTB) void k_mterms(MTermsK p) {
 
 // ---- fused bilinear forms, scalar, small uniform bases: rows of the local matrix per THREAD, owner-side reduction -------------------------------
 // (nh_gather.hip: the thread-per-element pass is ~5x cheaper than a workgroup pipeline for local matrices of this size; here with the term
-// list of nh_assemble_matrix_terms evaluated at the point in registers.)  Thread = (element, block of MB test functions); up to NF scalar
+// list of nh_assemble_matrix_terms evaluated at the point in registers.)  Thread = (element, block of MB test functions); every launch has MB == NBT, a
+// thread is an element (the parameter stays: without it the compiler orders the same instructions differently and takes up to 12 VGPRs more); up to NF scalar
 // fields on the test basis, their element coefficients in registers; the local matrix goes to the element-major scratch of NH_MATRIX_GATHER.
 struct LTermsK {
   i64 nelems;
@@ -882,10 +883,9 @@ __global__ __launch_bounds__(128) void k_local_terms(LTermsK p) {
     for (int n = 0; n < NBR; ++n) p.local[ie * (NBT * NBR) + (mb + m) * NBR + n] = A[m][n];
 }
 
-// k_local_terms re-arranged so that nothing of a point is computed twice (round 4).  The thread-per-row-block kernel above evaluates the geometry, the fields, the
-// polynomials and the term list of a point in EVERY row-block thread of the element (three times for configs[3]) and forms the pre-multiplied trial side W[n][a] for all
-// trial functions in each of them: ~14 k instructions per thread where the contraction needs ~3 k.  Here a workgroup of TPE * 64 threads owns 64 elements and walks over the
-// points in chunks of TPE:
+// k_local_terms for the 9 x 9 and 8 x 8 blocks (one thread per element there: 9 x 9 sums in 256 VGPRs, 0.85 against the 0.90 ms of row-block threads on C4 -- not worth
+// the occupancy), arranged so that nothing of a point is computed twice (round 4):
+// a workgroup of TPE * 64 threads owns 64 elements and walks over the points in chunks of TPE:
 //   phase A: wave w takes point q0 + w of the chunk, lane l element l -- geometry, fields, polynomials, term list ONCE per (element, point); the coefficient tensor is
 //            folded with the weight and the inverse Jacobian, C'[a][b] = w sum P[a][a'] Cq[a'][b'] P[b][b'] (P = diag(1, J^-1)), so that the contraction below needs the
 //            REFERENCE tables only; C' goes to LDS (double buffered: one barrier per chunk).  The point is wave-uniform: every table read of the phase is a broadcast.
@@ -1213,10 +1213,10 @@ __global__ __launch_bounds__(LT2_EPB *(NBR / NBK)) __attribute__((amdgpu_waves_p
     for (int j = 0; j < NBK; ++j) p.local[ieB * (NBT * NBR) + m * NBR + nb0 + j] = A[m][j];
 }
 
-// ---- fused linear forms, scalar blocks on small uniform bases: ONE THREAD per element ------------------------------------------------------------
+// ---- fused linear forms, scalar blocks on small uniform bases: one LANE per element --------------------------------------------------------------
 // The counterpart of k_local_terms for residuals: up to two scalar output blocks on ONE test basis (the residual blocks of a two-field system), up to
-// three scalar fields on the same basis with their element coefficients in registers; everything of a point -- field values, polynomial factors, the
-// integrand of every block -- stays in registers, and the NB sums per block go out with one atomic each.
+// three scalar fields on the same basis; everything of a point -- field values, polynomial factors, the integrand of every block -- stays in
+// registers, and the NB sums per block go out with one atomic each.
 struct VTermsK {
   i64 nelems;
   const int32_t *elist;
@@ -1235,179 +1235,7 @@ struct VTermsK {
   int ncls;  // k_local_vterms2: element classes whose tables a workgroup stages
 };
 
-template <int ND, int NB, int NF>
-__global__ __launch_bounds__(128) void k_local_vterms(VTermsK p) {
-  constexpr int S = 1 + ND, NG = 1 << ND;
-  __shared__ double tab[TABARG];
-  for (int i = threadIdx.x; i < p.tlen; i += blockDim.x) tab[i] = p.tabarg[i];
-  __syncthreads();
-  const i64 ie = (i64)blockIdx.x * blockDim.x + threadIdx.x;
-  if (ie >= p.nelems) return;
-  const i64 e = p.elist ? p.elist[ie] : ie;
-  const bool iso = p.geom.kind == NH_GEOM_ISO && p.geom.ngb == NG;
-  double X[NG][ND];
-  if (iso) {
-#pragma unroll
-    for (int a = 0; a < NG; ++a) {
-      const i64 v = p.geom.gdofs[e * NG + a];
-#pragma unroll
-      for (int i = 0; i < ND; ++i) X[a][i] = p.geom.verts[v * ND + i];
-    }
-  }
-  int dofs[NB];
-#pragma unroll
-  for (int n = 0; n < NB; ++n) dofs[n] = p.test.dofs[e * (i64)NB + n];
-  double ue[NF > 0 ? NF : 1][NB];
-#pragma unroll
-  for (int f = 0; f < NF; ++f)
-#pragma unroll
-    for (int n = 0; n < NB; ++n) ue[f][n] = p.u[f][dofs[n]];
-  double r[2][NB];
-#pragma unroll
-  for (int b = 0; b < 2; ++b)
-#pragma unroll
-    for (int m = 0; m < NB; ++m) r[b][m] = 0;
-  const double *Tt = p.test.T + bfn(p.test, e) * p.nq * S;
-  for (int q = 0; q < p.nq; ++q) {
-    double Ji[ND][ND], det;
-    if (iso) {
-      double J[ND][ND];
-#pragma unroll
-      for (int i = 0; i < ND; ++i)
-#pragma unroll
-        for (int j = 0; j < ND; ++j) J[i][j] = 0;
-#pragma unroll
-      for (int a = 0; a < NG; ++a) {
-        const double *tg = p.geom.gT + ((i64)a * p.nq + q) * S;
-#pragma unroll
-        for (int i = 0; i < ND; ++i)
-#pragma unroll
-          for (int j = 0; j < ND; ++j) J[i][j] += X[a][i] * tg[1 + j];
-      }
-      invert<ND>(J, Ji, det);
-      if (p.geom.bnd_axis >= 0) {
-        double s2 = 0;
-#pragma unroll
-        for (int j = 0; j < ND; ++j)
-#pragma unroll
-          for (int i = 0; i < ND; ++i)
-            if (j == p.geom.bnd_axis) s2 += Ji[j][i] * Ji[j][i];
-        det *= sqrt(s2);
-      }
-    } else
-      geometry_at<ND>(p.geom, e, q, p.nq, nullptr, Ji, det, nullptr);
-    const double w = p.weights[q] * fabs(det);
-    const i64 ip = ie * p.nq + q;
-    // reference tables of the point (shared by the fields and the test side), field values and physical gradients
-    double T[NB][S];
-#pragma unroll
-    for (int n = 0; n < NB; ++n)
-#pragma unroll
-      for (int s2 = 0; s2 < S; ++s2) T[n][s2] = Tt[((size_t)n * p.nq + q) * S + s2];
-    double U[NF > 0 ? NF : 1][S];
-#pragma unroll
-    for (int f = 0; f < NF; ++f) {
-      double rr[S];
-#pragma unroll
-      for (int s2 = 0; s2 < S; ++s2) rr[s2] = 0;
-#pragma unroll
-      for (int n = 0; n < NB; ++n)
-#pragma unroll
-        for (int s2 = 0; s2 < S; ++s2) rr[s2] += T[n][s2] * ue[f][n];
-      U[f][0] = rr[0];
-#pragma unroll
-      for (int i = 0; i < ND; ++i) {
-        double sum = 0;
-#pragma unroll
-        for (int j = 0; j < ND; ++j) sum += rr[1 + j] * Ji[j][i];
-        U[f][1 + i] = sum;
-      }
-    }
-    auto field = [&](int f, int s2) { return NF > 2 && f == 2 ? U[NF > 2 ? 2 : 0][s2] : NF > 1 && f == 1 ? U[NF > 1 ? 1 : 0][s2] : U[0][s2]; };
-    double pv[MAXP];
-#pragma unroll
-    for (int k = 0; k < MAXP; ++k) {
-      pv[k] = 1.;
-      if (k < p.npolys) {
-        const double *P = tab + p.poff[k];
-        const int nv = (int)P[0], nt = (int)P[1];
-        double x[4];
-#pragma unroll
-        for (int v = 0; v < 4; ++v) x[v] = v < nv ? field((int)P[2 + v], 0) : 1.;
-        double sum = 0;
-        for (int t2 = 0; t2 < nt; ++t2) {
-          const double *M = P + 6 + 5 * t2;
-          double mm = M[0];
-#pragma unroll
-          for (int v = 0; v < 4; ++v)
-            for (int k2 = (int)M[1 + v]; k2 > 0; --k2) mm *= x[v];
-          sum += mm;
-        }
-        pv[k] = sum;
-      }
-    }
-    // integrand of both blocks: sum of the terms
-    double G[2][S];
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int a = 0; a < S; ++a) G[b][a] = 0;
-    for (int t2 = 0; t2 < p.nterms; ++t2) {
-      const double *H = tab + p.toff[t2];
-      const int blk = (int)H[0], fld = (int)H[1], pol = (int)H[2], hasC = (int)H[3], hasf = (int)H[4];
-      double coef = p.scale[t2] ? p.scale[t2][ip] : 1.;
-      if (pol >= 0) coef *= pick(pv, pol);
-      if (p.qoff[t2]) {
-        const double *Q = tab + p.qoff[t2];
-        double sum = 0;
-#pragma unroll
-        for (int a = 0; a < S; ++a)
-#pragma unroll
-          for (int b = 0; b < S; ++b) sum += Q[2 + a * S + b] * field((int)Q[0], a) * field((int)Q[1], b);
-        coef *= sum;
-      }
-      const double *fv = H + 5, *C = fv + S;
-#pragma unroll
-      for (int a = 0; a < S; ++a) {
-        double sum = hasf ? fv[a] : 0.;
-        if (hasC) {
-#pragma unroll
-          for (int b = 0; b < S; ++b) sum += C[a * S + b] * field(fld, b);
-        }
-        if (blk == 0) G[0][a] += coef * sum;
-        else G[1][a] += coef * sum;
-      }
-    }
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      if (b >= p.nblocks) break;
-      double g[S];
-      g[0] = w * G[b][0];
-#pragma unroll
-      for (int j = 0; j < ND; ++j) {
-        double sum = 0;
-#pragma unroll
-        for (int i = 0; i < ND; ++i) sum += Ji[j][i] * G[b][1 + i];
-        g[1 + j] = w * sum;
-      }
-#pragma unroll
-      for (int m = 0; m < NB; ++m)
-#pragma unroll
-        for (int s2 = 0; s2 < S; ++s2) r[b][m] += T[m][s2] * g[s2];
-    }
-  }
-#pragma unroll
-  for (int b = 0; b < 2; ++b) {
-    if (b >= p.nblocks) break;
-#pragma unroll
-    for (int m = 0; m < NB; ++m) {
-      if (p.local[b]) p.local[b][e * NB + m] = r[b][m];
-      else atomicAdd(p.out[b] + dofs[m], r[b][m]);
-    }
-  }
-}
-
-// k_local_vterms for meshes of 2^14 elements and more, with the parallelism of the batched kernel and none of its run-time loops (round 4): a workgroup of LV2_NW waves
+// For meshes of 2^14 elements and more, with the parallelism of the batched kernel and none of its run-time loops (round 4): a workgroup of LV2_NW waves
 // owns 64 elements -- lane l of every wave is element l, wave w takes the points w, w + LV2_NW, ... -- so that the point is uniform over a wave (every table read a broadcast
 // from the staged tables of the element's class), each thread keeps partial sums r[block][m] of ITS points, and the waves' partial sums are added in wave order through
 // LDS at the end (deterministic).  configs[3] residual (262 144 elements, 25 points, 3 fields, 2 blocks): k_terms_multi 0.56 ms with 257 M wave instructions, 38 % of them
@@ -1740,37 +1568,28 @@ int local_terms(const nh_matrix_terms_args *a, const MTermsK &m, const std::vect
   for (int k = 0; k < MAXP; ++k) p.poff[k] = m.poff[k];
   p.tlen = (int)tab.size();
   std::copy(tab.begin(), tab.end(), p.tabarg);
-  int nmb = 0;
   const int key = (a->ndims * 100 + a->test.nb) * 100 + a->trial.nb;
-  switch (key) {
-    case 10202: nmb = 1; break;
-    case 10303: nmb = 1; break;
-    case 20404: nmb = 1; break;
-    case 20909: nmb = 3; break;  // (one thread per element, 9 x 9 sums in 256 VGPRs: 0.85 against 0.90 ms on C4 -- not worth the occupancy)
-    case 30808: nmb = 2; break;
-    default: return NH_OK;
-  }
+  const bool two_phase = key == 20909 || key == 30808;  // k_local_terms2; the smaller blocks: a thread is an element (k_local_terms)
+  if (!two_phase && key != 10202 && key != 10303 && key != 20404) return NH_OK;
   nh_pattern *pat = const_cast<nh_pattern *>(a->pattern);
   int rc;
   if ((rc = nh_gather_prepare(pat, a->test, a->elist_dev, s)) != NH_OK) return rc;
   double *scratch = nullptr;
   if ((rc = nh_gather_scratch((size_t)pat->emap_len, &scratch)) != NH_OK) return rc;
   p.local = scratch;
-  const i64 nthreads = a->nelems * nmb;
-  dim3 grid((unsigned)((nthreads + 127) / 128)), block(128);
+  dim3 grid((unsigned)((a->nelems + 127) / 128)), block(128);
   const bool same_tables = a->test.T_dev == a->trial.T_dev && a->test.tab_dev == a->trial.tab_dev;
   const size_t ldst = sizeof(double) * (size_t)a->nq * (1 + a->ndims) * (a->test.nb + (same_tables ? 0 : a->trial.nb));  // staged tables of one element class
   if (ldst > 48 * 1024) return NH_OK;  // (tables too large to stage: the batched kernel keeps the block)
+#ifdef NH_ABLATION
   if (getenv("NH_DEBUG_TERMS")) {
     fprintf(stderr, "local_terms: key %d nterms %d npolys %d nfields %d tlen %zu:", key, m.nterms, m.npolys, a->nfields, tab.size());
     for (int t = 0; t < m.nterms; ++t) fprintf(stderr, " [kind %d fld %d pol %d scale %d q %d]", (int)tab[m.toff[t]], (int)tab[m.toff[t] + 1], (int)tab[m.toff[t] + 2], m.scale[t] != nullptr, m.qoff[t] != 0);
     for (int k = 0; k < m.npolys; ++k) fprintf(stderr, " {poly nv %d nt %d}", (int)tab[m.poff[k]], (int)tab[m.poff[k] + 1]);
     fprintf(stderr, "\n");
   }
-  // the two-phase arrangement (k_local_terms2) for the blocks whose row-block threads repeat the point work; NUTILS_AMD_LOCAL_TERMS=1 keeps the kernel above
-  const bool two_phase = !(getenv("NUTILS_AMD_LOCAL_TERMS") && atoi(getenv("NUTILS_AMD_LOCAL_TERMS")) == 1);
-  bool launched2 = false;
-  if (two_phase && (key == 20909 || key == 30808)) {
+#endif
+  if (two_phase) {
     const int S2 = 1 + a->ndims, tpe = key == 20909 ? 3 : 4;
     p.ncls = a->nelems >= (1 << 16) ? 2 : LT2_CLS;  // (large meshes: occupancy; small ones, short rows: every class of the run staged)
     const size_t lds2_rest = sizeof(double) * ((NH_LT2_DB ? 2 : 1) * tpe * LT2_EPB * S2 * S2 + LT2_EPB * ((a->nfields * a->test.nb) | 1));
@@ -1799,22 +1618,20 @@ int local_terms(const nh_matrix_terms_args *a, const MTermsK &m, const std::vect
 #undef LT2F
 #undef LT2
 #undef LT2I
-    launched2 = true;
-  }
-#define LT(ND, NBT, NBR, MB)                                                                                  \
-  do {                                                                                                        \
-    if (a->nfields == 0) hipLaunchKernelGGL((k_local_terms<ND, NBT, NBR, MB, 0>), grid, block, ldst, s, p);      \
-    else if (a->nfields == 1) hipLaunchKernelGGL((k_local_terms<ND, NBT, NBR, MB, 1>), grid, block, ldst, s, p); \
-    else hipLaunchKernelGGL((k_local_terms<ND, NBT, NBR, MB, 2>), grid, block, ldst, s, p);                      \
+  } else {
+#define LT(ND, NBT, NBR)                                                                                  \
+  do {                                                                                                    \
+    if (a->nfields == 0) hipLaunchKernelGGL((k_local_terms<ND, NBT, NBR, NBT, 0>), grid, block, ldst, s, p);      \
+    else if (a->nfields == 1) hipLaunchKernelGGL((k_local_terms<ND, NBT, NBR, NBT, 1>), grid, block, ldst, s, p); \
+    else hipLaunchKernelGGL((k_local_terms<ND, NBT, NBR, NBT, 2>), grid, block, ldst, s, p);                      \
   } while (0)
-  if (!launched2) switch (key) {
-    case 10202: LT(1, 2, 2, 2); break;
-    case 10303: LT(1, 3, 3, 3); break;
-    case 20404: LT(2, 4, 4, 4); break;
-    case 20909: LT(2, 9, 9, 3); break;
-    case 30808: LT(3, 8, 8, 4); break;
-  }
+    switch (key) {
+      case 10202: LT(1, 2, 2); break;
+      case 10303: LT(1, 3, 3); break;
+      case 20404: LT(2, 4, 4); break;
+    }
 #undef LT
+  }
   NH_LAUNCH_CHECK();
   GSlots gs;
   memset(&gs, 0, sizeof gs);
@@ -1825,24 +1642,25 @@ int local_terms(const nh_matrix_terms_args *a, const MTermsK &m, const std::vect
   return NH_OK;
 }
 
-// thread-per-element residual for scalar blocks on ONE small uniform test basis with all fields on it; *done = false: not applicable
+// lane-per-element residual for scalar blocks on ONE small uniform test basis with all fields on it; *done = false: not applicable
 int local_vterms(const nh_terms_args *a, const TermsK &m, const std::vector<double> &tab, bool *done, hipStream_t s) {
   *done = false;
   const nh_basis &tb = a->blocks[0].test;
-  // (one thread per element pays when there are enough elements to hide its serial pass over the points: 2 M trilinear elements 0.82 ms against
-  // 1.16 ms of the batched kernel, but 262 144 elements of 25 points 0.78 against 0.45 ms -- there the lanes-over-points batches win)
+  // (a launch of its own pays from LV2_MIN_ELEMS elements on; shorter lists stay with the batched kernel)
   if (a->nelems < LV2_MIN_ELEMS || a->nfields > 3 || tab.size() > (size_t)TABARG || tb.off_dev || !tb.nb) return NH_OK;
   auto same = [&](const nh_basis &b) { return b.T_dev == tb.T_dev && b.dofs_dev == tb.dofs_dev && b.tab_dev == tb.tab_dev && b.off_dev == tb.off_dev && b.nb == tb.nb; };
   for (int b = 0; b < a->nblocks; ++b)
     if (a->blocks[b].nct != 1 || !same(a->blocks[b].test)) return NH_OK;
   for (int f = 0; f < a->nfields; ++f)
     if (a->fields[f].ncomp != 1 || !same(a->fields[f].basis)) return NH_OK;
+#ifdef NH_ABLATION
   if (getenv("NH_DEBUG_TERMS")) {
     fprintf(stderr, "local_vterms: nelems %lld nterms %d npolys %d nfields %d nblocks %d tlen %zu:", (long long)a->nelems, m.nterms, m.npolys, a->nfields, a->nblocks, tab.size());
     for (int t = 0; t < m.nterms; ++t) fprintf(stderr, " [blk %d fld %d pol %d C %d f %d scale %d q %d]", (int)tab[m.toff[t]], (int)tab[m.toff[t] + 1], (int)tab[m.toff[t] + 2], (int)tab[m.toff[t] + 3], (int)tab[m.toff[t] + 4], m.scale[t] != nullptr, m.qoff[t] != 0);
     for (int k = 0; k < m.npolys; ++k) fprintf(stderr, " {poly nv %d nt %d}", (int)tab[m.poff[k]], (int)tab[m.poff[k] + 1]);
     fprintf(stderr, "\n");
   }
+#endif
   VTermsK p;
   p.nelems = a->nelems, p.elist = a->elist_dev, p.nq = a->nq, p.weights = a->weights_dev;
   p.geom = m.geom, p.test = to_k(tb);
@@ -1854,17 +1672,14 @@ int local_vterms(const nh_terms_args *a, const TermsK &m, const std::vector<doub
   for (int k = 0; k < MAXP; ++k) p.poff[k] = m.poff[k];
   p.tlen = (int)tab.size();
   std::copy(tab.begin(), tab.end(), p.tabarg);
-  // the waves-over-points arrangement (k_local_vterms2); NUTILS_AMD_LOCAL_VTERMS=1 keeps one thread per element (from 2^20 elements on, as before round 4)
-  const bool waves_over_points = !(getenv("NUTILS_AMD_LOCAL_VTERMS") && atoi(getenv("NUTILS_AMD_LOCAL_VTERMS")) == 1);
-  if (waves_over_points) {
-    const int S2 = 1 + a->ndims, nb = tb.nb;
-    const size_t tabb = sizeof(double) * (((size_t)nb * a->nq * S2 + 1) & ~(size_t)1);
-    const size_t rest = sizeof(double) * std::max<size_t>((size_t)64 * ((a->nfields * nb) | 1), (size_t)(LV2_NW - 1) * 64 * ((2 * nb) | 1));
-    p.ncls = a->nelems >= (1 << 16) ? 2 : LT2_CLS;
-    while (p.ncls > 1 && p.ncls * tabb + rest > 64 * 1024) --p.ncls;
-    const size_t lds2 = p.ncls * tabb + rest;
-    if (lds2 <= 96 * 1024) {
-      dim3 grid2((unsigned)((a->nelems + 63) / 64)), block2(64 * LV2_NW);
+  const int S2 = 1 + a->ndims, nb = tb.nb;
+  const size_t tabb = sizeof(double) * (((size_t)nb * a->nq * S2 + 1) & ~(size_t)1);
+  const size_t rest = sizeof(double) * std::max<size_t>((size_t)64 * ((a->nfields * nb) | 1), (size_t)(LV2_NW - 1) * 64 * ((2 * nb) | 1));
+  p.ncls = a->nelems >= (1 << 16) ? 2 : LT2_CLS;
+  while (p.ncls > 1 && p.ncls * tabb + rest > 64 * 1024) --p.ncls;
+  const size_t lds2 = p.ncls * tabb + rest;
+  if (lds2 > 96 * 1024) return NH_OK;  // (tables too large to stage: the batched kernel keeps the list)
+  dim3 grid2((unsigned)((a->nelems + 63) / 64)), block2(64 * LV2_NW);
 #define LV2I(ND, NB, NF)                                                                                                                  \
   do {                                                                                                                                   \
     NH_CHECK_HIP(hipFuncSetAttribute((const void *)k_local_vterms2<ND, NB, NF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));  \
@@ -1877,42 +1692,16 @@ int local_vterms(const nh_terms_args *a, const TermsK &m, const std::vector<doub
     else if (a->nfields == 2) LV2I(ND, NB, 2);  \
     else LV2I(ND, NB, 3);                       \
   } while (0)
-      bool ok = true;
-      switch (a->ndims * 100 + tb.nb) {
-        case 102: LV2(1, 2); break;
-        case 103: LV2(1, 3); break;
-        case 204: LV2(2, 4); break;
-        case 209: LV2(2, 9); break;
-        case 308: LV2(3, 8); break;
-        default: ok = false;
-      }
-#undef LV2
-#undef LV2I
-      if (ok) {
-        NH_LAUNCH_CHECK();
-        *done = true;
-        return NH_OK;
-      }
-    }
-  }
-  if (a->nelems < (1 << 20)) return NH_OK;
-  dim3 grid((unsigned)((a->nelems + 127) / 128)), block(128);
-#define LV(ND, NB)                                                                                     \
-  do {                                                                                                 \
-    if (a->nfields == 0) hipLaunchKernelGGL((k_local_vterms<ND, NB, 0>), grid, block, 0, s, p);        \
-    else if (a->nfields == 1) hipLaunchKernelGGL((k_local_vterms<ND, NB, 1>), grid, block, 0, s, p);   \
-    else if (a->nfields == 2) hipLaunchKernelGGL((k_local_vterms<ND, NB, 2>), grid, block, 0, s, p);   \
-    else hipLaunchKernelGGL((k_local_vterms<ND, NB, 3>), grid, block, 0, s, p);                        \
-  } while (0)
   switch (a->ndims * 100 + tb.nb) {
-    case 102: LV(1, 2); break;
-    case 103: LV(1, 3); break;
-    case 204: LV(2, 4); break;
-    case 209: LV(2, 9); break;
-    case 308: LV(3, 8); break;
+    case 102: LV2(1, 2); break;
+    case 103: LV2(1, 3); break;
+    case 204: LV2(2, 4); break;
+    case 209: LV2(2, 9); break;
+    case 308: LV2(3, 8); break;
     default: return NH_OK;
   }
-#undef LV
+#undef LV2
+#undef LV2I
   NH_LAUNCH_CHECK();
   *done = true;
   return NH_OK;

@@ -811,9 +811,12 @@ static int launch_march_inst(const nh_p1hex_args *a, P1Args &p, void *stream) {
 #ifdef NH_ABLATION
   p.debug = getenv("NH_P1HEX_DEBUG") ? atoi(getenv("NH_P1HEX_DEBUG")) : 0;
 #endif
-  // measured optimum at 64^3 .. 256^3 (16 = unweighted: +7 .. +18 %); the tuning override is read once per process and clamped to a sane range
+  // measured optimum at 64^3 .. 256^3 (16 = unweighted: +7 .. +18 %)
+  p.wbnd = 20;
+#ifdef NH_ABLATION  // the tuning override is read once per process and clamped to a sane range
   static const int wbnd_env = getenv("NH_P1HEX_WBND") ? std::min(64, std::max(8, atoi(getenv("NH_P1HEX_WBND")))) : 20;
   p.wbnd = getenv("NH_P1HEX_STAGE_LATE") ? -wbnd_env : wbnd_env;
+#endif
   constexpr int TJ = 16, TK = 16, L = 2, NTM = L * TJ * TK, NS = VEC ? 1 : 15, VW = VEC ? 4 : 3;
   // (per-step path of a Newton loop / of a multi-GPU slab whose kernel lasts ~20 us: device queries and the LDS attribute once per process)
   // (function attributes and the CU count belong to a DEVICE: remembered per device index; the library is driven by one host thread, include/nutils_hip.h)

@@ -153,7 +153,7 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(USE0 ? 2
             p.local[kbase + m * (m + 1) / 2 + n] = K[i][j][0][0];
           } else {
             p.local[kbase + (i64)m * knb + n] = K[i][j][0][0];
-            if (m != n && p.sym != 2) p.local[kbase + (i64)n * knb + m] = K[i][j][0][0];
+            if (m != n) p.local[kbase + (i64)n * knb + m] = K[i][j][0][0];
           }
           continue;
         } else
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(USE0 ? 2
         if (form.mask[0][0] && form.mask[0][1] && form.mask[1][0] && form.mask[1][1]) {  // (all component blocks present: 16-byte stores)
           *reinterpret_cast<double2 *>(dst) = double2{K[i][j][0][0], K[i][j][0][1]};
           *reinterpret_cast<double2 *>(dst + 2) = double2{K[i][j][1][0], K[i][j][1][1]};
-          if (m != n && p.sym != 2) {
+          if (m != n) {
             *reinterpret_cast<double2 *>(dst2) = double2{K[i][j][0][0], K[i][j][1][0]};
             *reinterpret_cast<double2 *>(dst2 + 2) = double2{K[i][j][0][1], K[i][j][1][1]};
           }
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(USE0 ? 2
             for (int d = 0; d < NC; ++d) {
               if (!form.mask[c][d]) continue;
               dst[c * NC + d] = K[i][j][c][d];
-              if (m != n && p.sym != 2) dst2[d * NC + c] = K[i][j][c][d];
+              if (m != n) dst2[d * NC + c] = K[i][j][c][d];
             }
         }
       }
@@ -292,7 +292,11 @@ static GramShape nh_gram_sym_shape(const MatK &q, const FormK &form, int ndims) 
   if (q.nq > 64 || q.nq * q.maxnbt > 640 || B > 256) return g;  // (large tables: the generic kernel chunks the points)
   // (elements, waves) per workgroup: the fullest lanes among the instantiated shapes
   static const int shapes[][2] = {{4, 4}, {3, 4}, {2, 4}, {1, 4}};
+#ifdef NH_ABLATION
   static const int force = getenv("NUTILS_AMD_GRAM_SYM_SHAPE") ? atoi(getenv("NUTILS_AMD_GRAM_SYM_SHAPE")) : 0;  // e.g. 34: three elements on four waves
+#else
+  constexpr int force = 0;
+#endif
   double best = 0;
   for (auto &sh : shapes) {
     if (sh[0] * B > 64 * sh[1] || (force && force != sh[0] * 10 + sh[1])) continue;

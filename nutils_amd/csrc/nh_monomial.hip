@@ -67,7 +67,11 @@ int nh_index_copy(int64_t n, const double *src_dev, const int64_t *src_index_dev
   hipPointerAttribute_t attr;
   const bool host = hipPointerGetAttributes(&attr, dst) == hipSuccess && attr.type == hipMemoryTypeHost;
   if (!host) (void)hipGetLastError();
+#ifdef NH_ABLATION
   static const int hostwgs = getenv("NH_INDEX_COPY_WGS") ? atoi(getenv("NH_INDEX_COPY_WGS")) : 64;
+#else
+  constexpr int hostwgs = 64;
+#endif
   const unsigned grid = (unsigned)std::min<i64>((n + 255) / 256, host ? hostwgs : 256 * 32);
   hipLaunchKernelGGL(k_index_copy, dim3(grid), dim3(256), 0, nh_stream(stream), (i64)n, src_dev, (const i64 *)src_index_dev, (const i64 *)dst_index_dev, dst);
   NH_LAUNCH_CHECK();

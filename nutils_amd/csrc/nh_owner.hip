@@ -701,7 +701,11 @@ static int nh_owner_prepare(nh_pattern *p, const nh_matrix_args *a, int sd, bool
     OP_CHECK(bp_alloc(t, &flags, 3));
     // rows per block: the largest candidate whose fullest block fits the LDS budget (two workgroups per CU)
     size_t budget = 80 * 1024;
+    int forced = 0;
+#ifdef NH_ABLATION
     if (getenv("NH_OWNER_LDS")) budget = (size_t)std::max(16, std::min(160, atoi(getenv("NH_OWNER_LDS")))) * 1024;
+    if (getenv("NH_OWNER_ROWS")) forced = std::max(1, std::min(256, atoi(getenv("NH_OWNER_ROWS"))));
+#endif
     int R = 0, vmax = 0, nblocks = 0;
     i64 nvisits = 0;
     // (elements of more than 9 functions -- triquadratic: 27 -- take their points in chunks and hold the sums of a block's contributions in registers meanwhile: boxes of at
@@ -709,8 +713,6 @@ static int nh_owner_prepare(nh_pattern *p, const nh_matrix_args *a, int sd, bool
     const bool big = nbt > 9;
     // (boxes of up to 24 rows often have no more visits than those of up to 16 -- 45 at most on a hexahedral mesh -- and are fewer: 96^3 trilinear elasticity 1.39 -> 1.35 ms)
     const int cand[] = {64, 32, 24, 16, 8, 4, 2, 1};
-    const size_t cand_budget[] = {0, 0, 0, 0, 0, 0, 0, 0};  // 0: the common budget (two workgroups per CU)
-    int forced = getenv("NH_OWNER_ROWS") ? std::max(1, std::min(256, atoi(getenv("NH_OWNER_ROWS")))) : 0;
     int qc = a->nq;
     for (int ci = big ? 4 : 0; ci < 8; ++ci) {
       const int Rc = forced ? forced : cand[ci];
@@ -723,11 +725,12 @@ static int nh_owner_prepare(nh_pattern *p, const nh_matrix_args *a, int sd, bool
       OP_CHECK(hipStreamSynchronize(s));
       for (int parts = 1; parts <= (big ? 8 : 1) && !R; ++parts) {
         const int q = (a->nq + parts - 1) / parts;
-        const size_t bud = (!forced && cand_budget[ci] && !getenv("NH_OWNER_LDS")) ? cand_budget[ci] : budget;
-        if (hflags[2] < 4096 && owner_lds(Rc, hflags[2], a->nq, q, nbt, a->ndims, sd, isof, ldst, iso, parts > 1) <= bud) R = Rc, vmax = hflags[2], qc = q;  // (without the staged vertices if need be)
+        if (hflags[2] < 4096 && owner_lds(Rc, hflags[2], a->nq, q, nbt, a->ndims, sd, isof, ldst, iso, parts > 1) <= budget) R = Rc, vmax = hflags[2], qc = q;  // (without the staged vertices if need be)
       }
       if (R) break;
+#ifdef NH_ABLATION
       if (getenv("NH_OWNER_VERBOSE")) fprintf(stderr, "nh_owner plan: %d rows per block -> at most %d visits, %zu B of LDS: over the budget\n", Rc, hflags[2], owner_lds(Rc, hflags[2], a->nq, a->nq, nbt, a->ndims, sd, isof, ldst, iso));
+#endif
       if (forced) break;
       for (int i = tn; i < t.n; ++i) hipFree(t.ptr[i]);  // (this candidate's arrays)
       t.n = tn;
@@ -754,7 +757,11 @@ static int nh_owner_prepare(nh_pattern *p, const nh_matrix_args *a, int sd, bool
     OP_CHECK(hipMemcpyAsync(hflags, flags, sizeof hflags, hipMemcpyDeviceToHost, s));
     OP_CHECK(hipStreamSynchronize(s));
     // entries of at most 16 contributions (hexahedra: 8, quadrilaterals: 4): kept inside rows of 16 lanes, summed with DPP row shifts instead of ds_bpermute
+#ifdef NH_ABLATION
     const int rows16 = hflags[1] <= 16 && !getenv("NH_OWNER_NO_DPP");
+#else
+    const int rows16 = hflags[1] <= 16;
+#endif
     if (rows16) {
       hipLaunchKernelGGL((k_op_pack<false>), dim3((unsigned)((nblocks + 63) / 64)), dim3(64), 0, s, nblocks, bptr, bstart, key2, val2, nch, (const i64 *)nullptr, (uint32_t *)nullptr,
                          (uint32_t *)nullptr, flags + 1, 1);
@@ -794,10 +801,12 @@ static int nh_owner_prepare(nh_pattern *p, const nh_matrix_args *a, int sd, bool
     OP_CHECK(hipMalloc((void **)&o->prl, sizeof(int32_t) * (size_t)std::max<i64>(nrows, 1)));
     hipLaunchKernelGGL(k_op_rowinfo, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, s, nrows, o->order, p->srowptr, o->prs, o->prl);
     OP_CHECK(hipGetLastError());
+#ifdef NH_ABLATION
     if (getenv("NH_OWNER_VERBOSE"))
       fprintf(stderr, "nh_owner plan: %d blocks of %d rows, %lld visits (%.2f per element, at most %d per block), %lld chunks for %lld items (%.2f lanes used), entries of up to %d items, %zu B of LDS\n",
               nblocks, R, (long long)nvisits, (double)nvisits / (double)ne, vmax, (long long)nchunks, (long long)ni, (double)ni / (64. * (double)nchunks), hflags[1],
               owner_lds(R, vmax, a->nq, qc, nbt, a->ndims, sd, isof, ldst, iso));
+#endif
   }
 done:
 #undef OP_CHECK
@@ -868,7 +877,9 @@ int nh_owner_vector(const nh_matrix_args *a, const GSlots &slots, bool *done, hi
   // the staged vertices are given up where they cost a workgroup per CU (two of 80 kB fit, three of 53 kB)
   const size_t lds0 = owner_lds(o->rows_per_block, o->max_visits, a->nq, qc, a->test.nb, a->ndims, sd, isof, ldst, iso, false);
   bool xlds = iso && ((160 * 1024 / lds0 == 160 * 1024 / std::max<size_t>(lds, 1)) || chunked) && lds <= 160 * 1024;
+#ifdef NH_ABLATION
   if (getenv("NH_OWNER_XLDS")) xlds = iso && atoi(getenv("NH_OWNER_XLDS")) != 0;
+#endif
   if (!xlds) lds = lds0;
   if (lds > 160 * 1024) return NH_OK;  // (a plan built for other tables / forms: the caller keeps its other paths)
   p.nq = a->nq;
@@ -894,7 +905,9 @@ int nh_owner_vector(const nh_matrix_args *a, const GSlots &slots, bool *done, hi
   p.vlist = o->vlist, p.vptr = o->vptr, p.cptr = o->cptr, p.bptr = o->bptr, p.isrc = o->isrc, p.idst = o->idst;
   // threads: enough waves for the chunks of a block, and for the latencies of phase 1 when one block takes most of a CU's LDS
   int nt = lds > 80 * 1024 ? 1024 : lds > 52 * 1024 ? 512 : 256;
+#ifdef NH_ABLATION
   if (getenv("NH_OWNER_NT")) nt = std::max(64, std::min(OWN_NT_MAX, atoi(getenv("NH_OWNER_NT")) & ~63));
+#endif
   if (!xlds) nt = std::min(nt, OWN_NT_MAX / 2);
   if (big) nt = 256;
 #ifdef NH_ABLATION

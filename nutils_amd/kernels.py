@@ -171,8 +171,8 @@ def basis(T, dofs, nb=0, off=None, tab=None):
     return b
 
 
-FUSED_SIZES = {(1, 2), (1, 3), (2, 3), (2, 4), (2, 9), (3, 4), (3, 8)}  # (dimension, functions per element) of the owner-block kernels (NH_MATRIX_FUSED)
-# ... and those for which they are the DEFAULT: measured faster than the gather with the ordered sums (tools/generic_probe.py, round 5, ordered rounds: 128^3 trilinear
+# (dimension, functions per element) for which the owner-block kernels (NH_MATRIX_FUSED; they cover (1, 2), (1, 3), (2, 3), (2, 4), (2, 9), (3, 4), (3, 8) with fused=True)
+# are the DEFAULT: measured faster than the gather with the ordered sums (tools/generic_probe.py, round 5, ordered rounds: 128^3 trilinear
 # 0.55 against 0.90 ms; 2048^2 bilinear 0.43 against 0.45, 1024^2 quadratic splines 0.43 against 0.59, but 1024^2 biquadratic 0.88 against 0.69 ms -- the 2-D sizes stay
 # with the gather)
 FUSED_DEFAULT = {(3, 8)}
@@ -214,7 +214,7 @@ def assemble_matrix(*, nelems, ndims, nq, weights, geom, test, trial, nct, ncr, 
     if elist is None and emap_offset == 0 and not os.environ.get('NUTILS_AMD_NO_BUCKETS'):
         args.pattern = pattern._handle  # ragged bases: launches per size class of the pattern
     whole = emap_offset == 0 and not flags and not first_touch and nelems == pattern.nelems
-    if (not fused and gather is None and not os.environ.get('NUTILS_AMD_NO_FUSED') and whole and elist is None and nct == ncr == 1 and cq is None and ((ndims, test.nb) in FUSED_DEFAULT or os.environ.get('NUTILS_AMD_FUSED') and (ndims, test.nb) in FUSED_SIZES)
+    if (not fused and gather is None and not os.environ.get('NUTILS_AMD_NO_FUSED') and whole and elist is None and nct == ncr == 1 and cq is None and (ndims, test.nb) in FUSED_DEFAULT
             and test.nb == trial.nb and test.dofs_dev == trial.dofs_dev and not test.off_dev):
         # (default since round 4 for the blocks the owner-block kernels cover: one pass, 1.5 x instead of 4.6 x the algorithmic traffic, and -- with the
         # turns of the block plan -- bit-reproducible like the gather)

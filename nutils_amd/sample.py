@@ -800,7 +800,7 @@ class _MatrixPlan:
             return None
         if basis.dofs_shape != tuple(n * basis.degree + 1 for n in basis.shape) or os.environ.get('NUTILS_AMD_NO_FIRST_TOUCH'):
             return None  # (periodic axes: the neighbour across the seam)
-        if not (smp.nlist >= COLOR_THRESHOLD and basis.nb >= 16 and _colors(smp, basis)) or os.environ.get('NUTILS_AMD_NO_COLORS'):
+        if not (smp.nlist >= COLOR_THRESHOLD and basis.nb >= 16 and _colors(smp, basis)):
             return None
         if self._rows_pass(smp, itg):
             return None  # (not assembled colour by colour)
@@ -1038,8 +1038,7 @@ class _MatrixPlan:
                 kernels.assemble_matrix(nelems=smp.nlist, elist=smp._elist_dev, cq=cq, fresh=fresh[0], **common_q)
                 fresh[0] = False
                 continue
-            if (itg.test.basis is itg.trial.basis and smp.nlist >= COLOR_THRESHOLD and tt.nb >= 16 and not self._rows_pass(smp, itg)
-                    and not os.environ.get('NUTILS_AMD_NO_COLORS')):  # (small local matrices: 8 coloured launches measured slower than atomics, 4.7 vs 4.0 ms)
+            if itg.test.basis is itg.trial.basis and smp.nlist >= COLOR_THRESHOLD and tt.nb >= 16 and not self._rows_pass(smp, itg):  # (small local matrices: 8 coloured launches measured slower than atomics, 4.7 vs 4.0 ms)
                 colors = _colors(smp, itg.test.basis)
             if colors:
                 if fresh[0]:
