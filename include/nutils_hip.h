@@ -737,6 +737,26 @@ int nh_csr_spmv_dots(const nh_csr *A, const double *x_dev, const double *w_dev, 
 int nh_bicgstab_init(int64_t n, const double *dinv_dev, const double *r_dev, double *rhat_dev, double *p_dev, double *phat_dev, double *work_dev, void *stream);
 int nh_bicgstab_iterate(const nh_csr *A, const unsigned char *rowmask_dev, const double *dinv_dev, double *x_dev, double *r_dev, const double *rhat_dev, double *p_dev,
                         double *v_dev, double *s_dev, double *t_dev, double *phat_dev, double *shat_dev, double *work_dev, double stop_rr, int niter, void *stream);
+/* Restarted GMRES for ANY square A, right-preconditioned with M^-1 = dinv (Jacobi) or the identity (dinv_dev NULL; with a fixed M this is also flexible GMRES),
+ * entirely on the device and by the rules above: a row mask on which every vector vanishes, nothing atomic, every sum in a fixed order, no scalar visits the
+ * host, repeated solves are bit-identical.  V_dev: restart + 1 basis vectors of n doubles, one after the other; z_dev, w_dev: n doubles; work_dev:
+ * nh_gmres_work_doubles(restart) doubles (-1 and an error for restart < 1).  Of the work array the host reads work[0] = the squared residual norm of the
+ * least-squares problem (after nh_gmres_init: r . r), work[1] = 1. once a new direction has vanished or was not finite, work[2] = the Arnoldi steps taken since
+ * nh_gmres_init (exact, whatever niter was).
+ * nh_gmres_init starts a cycle from a given r: v_0 = r / |r|, z = dinv v_0, g = |r| e_0; it marks the cycle as finished if r = 0.
+ * nh_gmres_iterate enqueues niter Arnoldi steps of nine launches; the device knows which column it is at.  Step j: w = mask(A z); classical Gram-Schmidt
+ * twice (the dots of w with v_0 .. v_j in one kernel that takes the basis vectors eight at a time, a small launch that sums the partials, w -= V h in one
+ * kernel, the second time with the partials of w . w); one workgroup forms column j of the Hessenberg matrix from the two passes, applies the stored Givens
+ * rotations, makes the new one, rotates g and writes work[0 .. 2]; v_(j+1) = w / h_(j+1,j), z = dinv v_(j+1).  The steps stop moving anything once
+ * work[0] <= stop_rr, once restart columns are taken, or once a direction vanishes: |w| after the two passes within 2^-40 of |A z| before them.  With a pivot
+ * left that is the lucky breakdown (the column is taken, work[0] = 0); with none (a zero column, say) or with a non-finite column the column is not taken.
+ * nh_gmres_update forms x += dinv V y, y from the triangular system of the columns taken (one workgroup, then one kernel); whether the true residual is then
+ * within the bound is the caller's to find out.  Vectors of even length on 16-byte boundaries are read and written two doubles at a time. */
+int64_t nh_gmres_work_doubles(int restart);
+int nh_gmres_init(int64_t n, int restart, const double *dinv_dev, const double *r_dev, double *V_dev, double *z_dev, double *work_dev, void *stream);
+int nh_gmres_iterate(const nh_csr *A, const unsigned char *rowmask_dev, const double *dinv_dev, double *V_dev, double *z_dev, double *w_dev, double *work_dev, int restart,
+                     double stop_rr, int niter, void *stream);
+int nh_gmres_update(int64_t n, int restart, const double *dinv_dev, const double *V_dev, double *x_dev, double *work_dev, void *stream);
 
 #ifdef __cplusplus
 }

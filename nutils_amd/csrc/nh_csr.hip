@@ -10,6 +10,7 @@
 //     DOT = 1: additionally the workgroup's share of x . y goes to partial[blockIdx.x] (the p . Ap of a CG step).
 //     DOT = 2: the shares of w . y and y . y, w a vector of its own, go to partial[blockIdx.x] and partial2[blockIdx.x] (the two products of a BiCGStab
 //     step); the kernel does nothing at all when *skip != 0 (the iteration has stopped).
+//     DOT = 3: no dots, only the skip cell (the product of a GMRES step, whose dots are the Gram-Schmidt kernels').
 //   * k_csr_support<L, Idx>: the support of the matrix above a tolerance, by the product's mapping (L lanes per row, a wave reads one contiguous span):
 //     a lane that meets |a| > tol stores the byte 1 to colsupp[col] and remembers it for the row, whose L lanes are folded with __shfl_xor before lane 0
 //     stores rowsupp[row].  Lanes that meet the same column store the same byte to the same address: plain vector byte stores, nothing atomic, and since
@@ -22,6 +23,8 @@
 #include "nh_common.h"
 #include <algorithm>
 #include <climits>
+#include <cstdint>
+#include <initializer_list>
 
 namespace {
 
@@ -53,7 +56,7 @@ template <int L, class Idx, int DOT>
 __global__ __launch_bounds__(WG) void k_csr_spmv(i64 nrows, const i64 *__restrict__ rowptr, const Idx *__restrict__ col, const double *__restrict__ values,
                                                  const double *__restrict__ x, double alpha, double beta, const double *b, const unsigned char *__restrict__ mask, double *y,
                                                  double *partial, const double *__restrict__ w, double *partial2, const double *skip) {
-  if (DOT == 2 && skip && *skip != 0.) return;
+  if (DOT >= 2 && skip && *skip != 0.) return;
   constexpr int G = WG / L;  // rows per workgroup and step
   const int lane = threadIdx.x & (L - 1);
   double dot = 0, dot2 = 0;
@@ -83,7 +86,7 @@ __global__ __launch_bounds__(WG) void k_csr_spmv(i64 nrows, const i64 *__restric
       }
     }
   }
-  if (DOT) {
+  if (DOT == 1 || DOT == 2) {
     __shared__ double lds[4];
     dot = block_sum(dot, lds);
     if (DOT == 2) dot2 = block_sum(dot2, lds);
@@ -407,6 +410,320 @@ __global__ __launch_bounds__(WG) void k_spmv_dots_sum(int nwy, double *work) {
   }
 }
 
+// ---- restarted GMRES: right-preconditioned, M^-1 = dinv or the identity (with a fixed M flexible and right-preconditioned GMRES are one iteration); all
+// vectors vanish on masked rows.  V holds restart + 1 basis vectors of n doubles, one after the other.  Arnoldi step j (j = G_COUNT, read on the device:
+// the host does not know where in a cycle it enqueues) is
+//   w = mask(A z)                                                                       (k_csr_spmv, DOT = 3)
+//   twice (classical Gram-Schmidt; one pass leaves V^T V - I at 2e-9 after 72 steps on a 1480-row matrix, at 7e-6 by the time an unrestarted solve has converged):
+//     dots:     partials of v_k . w, k = 0 .. j, the basis vectors taken GS_CHUNK at a time with one accumulator each
+//     dots_sum: h[k] = the partials summed, workgroup k sums those of v_k               (G_H1 in the first pass, G_H2 in the second)
+//     axpy:     w -= sum_k h[k] v_k, k ascending; in the second pass also the partials of w . w
+//   scalars:    one workgroup: column j of the Hessenberg matrix is h1 + h2 above h_(j+1,j) = |w|; the stored rotations are applied to it, a new one
+//               annihilates h_(j+1,j), g is rotated, G_RR = g_(j+1)^2 is the squared residual norm of the least-squares problem; status and count
+//   normalize:  v_(j+1) = w / h_(j+1,j), z = dinv v_(j+1)                               (also the v_0 = r / |r| of nh_gmres_init)
+// Every kernel reads the status G_ST first and does nothing unless it is 0; k_gmres_scalars (and the init) is its only writer, as of every cell of the
+// head.  A status is 0 (iterate), ST_DONE (G_RR <= stop_rr, or the new direction vanished with a pivot left: the lucky breakdown), ST_BAD (the column
+// cannot be taken: no pivot, or not finite) or ST_FULL (restart columns taken).  A direction "vanishes" when |w| after the two passes is within GS_VANISH
+// of the norm of the column, sqrt(sum h^2 + |w|^2) = |A z| before them: what is left of w is then rounding noise, whose normalisation would be a basis
+// vector of noise.  G_FLAG is raised with every vanished or non-finite direction; what it means is the host's to decide from the true residual.
+enum {
+  G_RR = 0,     // g_(j+1)^2 (after init: r . r)       <- scalars, init
+  G_FLAG = 1,   // 1. after a vanished or non-finite direction
+  G_COUNT = 2,  // columns taken in this cycle: the j of the next step
+  G_ST = 3,     // status
+  G_HN = 4,     // the divisor of normalize: |r| or h_(j+1,j)
+  G_HEAD = 8
+};
+constexpr double ST_FULL = 3.;
+constexpr int GS_CHUNK = 8;            // basis vectors per pass over w in the Gram-Schmidt kernels (kernels.GMRES_CHUNK)
+constexpr double GS_VANISH = 0x1p-40;  // (the rounding of a two-pass Gram-Schmidt step is (j + n) u |A z| at the very most: 2^-33 of it for 2^20 rows)
+
+// where the arrays of the work array start, m = restart: h1, h2 (the two passes' dots), cs, sn (rotations), g, y (m + 1 each), r (the triangular factor, column j
+// at r + j (m + 1)), wwp (partials of w . w or r . r), hp (partials of v_k . w at hp + k VEC_MAX_WGS)
+struct GmresCells {
+  i64 h1, h2, cs, sn, g, y, r, wwp, hp, end;
+};
+__host__ __device__ inline GmresCells gmres_cells(int m) {
+  GmresCells c;
+  const i64 m1 = (i64)m + 1;
+  c.h1 = G_HEAD;
+  c.h2 = c.h1 + m1;
+  c.cs = c.h2 + m1;
+  c.sn = c.cs + m1;
+  c.g = c.sn + m1;
+  c.y = c.g + m1;
+  c.r = c.y + m1;
+  c.wwp = c.r + m1 * m;
+  c.hp = c.wwp + VEC_MAX_WGS;
+  c.end = c.hp + (i64)m * VEC_MAX_WGS;
+  return c;
+}
+
+// VW doubles of a vector in one load or store (VW = 2: 16 bytes, for vectors of even length on 16-byte boundaries)
+template <int VW>
+struct Pack {
+  double v[VW];
+};
+template <int VW>
+__device__ __forceinline__ Pack<VW> ld(const double *p) {
+  Pack<VW> a;
+  if constexpr (VW == 2) {
+    const double2 t = *reinterpret_cast<const double2 *>(p);
+    a.v[0] = t.x;
+    a.v[1] = t.y;
+  } else
+    a.v[0] = *p;
+  return a;
+}
+template <int VW>
+__device__ __forceinline__ void st(double *p, const Pack<VW> &a) {
+  if constexpr (VW == 2)
+    *reinterpret_cast<double2 *>(p) = make_double2(a.v[0], a.v[1]);
+  else
+    *p = a.v[0];
+}
+
+// block_sum of C numbers at once
+template <int C>
+__device__ __forceinline__ void block_sum_n(double (&s)[C], double *lds) {
+#pragma unroll
+  for (int c = 0; c < C; ++c)
+#pragma unroll
+    for (int o = 32; o; o >>= 1) s[c] += __shfl_xor(s[c], o, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int c = 0; c < C; ++c) lds[4 * c + (threadIdx.x >> 6)] = s[c];
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < C; ++c) s[c] = ((lds[4 * c] + lds[4 * c + 1]) + lds[4 * c + 2]) + lds[4 * c + 3];
+}
+
+// the column the step works on: G_COUNT, kept inside the basis whatever the cell holds
+__device__ __forceinline__ int gmres_column(const double *work, int m) { return max(0, min((int)work[G_COUNT], m - 1)); }
+
+#define NH_GS_ROWS(i) for (i64 i = ((i64)blockIdx.x * WG + threadIdx.x) * VW; i < n; i += (i64)gridDim.x * WG * VW)
+
+// partials of r . r
+__global__ __launch_bounds__(WG) void k_gmres_norm(i64 n, int m, const double *__restrict__ r, double *work) {
+  __shared__ double lds[4];
+  double rr = 0;
+  for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < n; i += (i64)gridDim.x * WG) rr += r[i] * r[i];
+  rr = block_sum(rr, lds);
+  if (threadIdx.x == 0) work[gmres_cells(m).wwp + blockIdx.x] = rr;
+}
+
+__global__ __launch_bounds__(WG) void k_gmres_init_scalars(int nparts, int m, double *work) {
+  __shared__ double lds[4];
+  const GmresCells c = gmres_cells(m);
+  const double rr = partial_sum(work + c.wwp, nparts, lds);
+  if (threadIdx.x == 0) {
+    const bool bad = !finite(rr);
+    const double beta = sqrt(rr);
+    work[G_RR] = rr;
+    work[G_FLAG] = bad ? 1. : 0.;
+    work[G_COUNT] = 0.;
+    work[G_ST] = bad ? ST_BAD : rr == 0. ? ST_DONE : 0.;  // (a residual of zero: nothing to do, and nothing to normalise)
+    work[G_HN] = beta;
+    work[c.g] = beta;
+  }
+}
+
+// v_count = src / G_HN, z = dinv v_count (or v_count); src is w, or r at the start of a cycle
+template <int VW>
+__global__ __launch_bounds__(WG) void k_gmres_normalize(i64 n, int m, const double *__restrict__ dinv, const double *__restrict__ src, double *__restrict__ V,
+                                                        double *__restrict__ z, const double *__restrict__ work) {
+  if (work[G_ST] != 0.) return;
+  const double hn = work[G_HN];
+  double *v = V + (i64)max(0, min((int)work[G_COUNT], m)) * n;
+  NH_GS_ROWS(i) {
+    Pack<VW> a = ld<VW>(src + i);
+#pragma unroll
+    for (int e = 0; e < VW; ++e) a.v[e] /= hn;
+    st<VW>(v + i, a);
+    if (dinv) {
+      const Pack<VW> d = ld<VW>(dinv + i);
+#pragma unroll
+      for (int e = 0; e < VW; ++e) a.v[e] *= d.v[e];
+    }
+    st<VW>(z + i, a);
+  }
+}
+
+// partials of v_k . w, k = 0 .. j: w and every basis vector are read once per chunk of C vectors
+template <int C, int VW>
+__global__ __launch_bounds__(WG) void k_gmres_dots(i64 n, int m, const double *__restrict__ V, const double *__restrict__ w, double *work) {
+  if (work[G_ST] != 0.) return;
+  __shared__ double lds[4 * C];
+  const int j = gmres_column(work, m);
+  double *hp = work + gmres_cells(m).hp + blockIdx.x;
+  for (int k0 = 0; k0 <= j; k0 += C) {
+    const int nk = min(C, j + 1 - k0);
+    const double *v0 = V + (i64)k0 * n;
+    double acc[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) acc[c] = 0;
+    NH_GS_ROWS(i) {
+      const Pack<VW> wi = ld<VW>(w + i);
+      Pack<VW> vi[C];
+#pragma unroll
+      for (int c = 0; c < C; ++c)
+        if (c < nk) vi[c] = ld<VW>(v0 + (i64)c * n + i);
+#pragma unroll
+      for (int c = 0; c < C; ++c)
+        if (c < nk)
+#pragma unroll
+          for (int e = 0; e < VW; ++e) acc[c] += vi[c].v[e] * wi.v[e];
+    }
+    block_sum_n<C>(acc, lds);
+    if (threadIdx.x == 0)
+#pragma unroll
+      for (int c = 0; c < C; ++c)
+        if (c < nk) hp[(i64)(k0 + c) * VEC_MAX_WGS] = acc[c];
+  }
+}
+
+// h[k] = the partials of v_k . w in a fixed order; a workgroup per k
+__global__ __launch_bounds__(WG) void k_gmres_dots_sum(int nparts, int m, int second, double *work) {
+  if (work[G_ST] != 0.) return;
+  __shared__ double lds[4];
+  const GmresCells c = gmres_cells(m);
+  const int j = gmres_column(work, m);
+  for (int k = blockIdx.x; k <= j; k += gridDim.x) {
+    const double h = partial_sum(work + c.hp + (i64)k * VEC_MAX_WGS, nparts, lds);
+    if (threadIdx.x == 0) work[(second ? c.h2 : c.h1) + k] = h;
+  }
+}
+
+// w -= sum_k h[k] v_k, k ascending; WW: the partials of the new w . w
+template <int C, int VW, bool WW>
+__global__ __launch_bounds__(WG) void k_gmres_axpy(i64 n, int m, int second, const double *__restrict__ V, double *__restrict__ w, double *work) {
+  if (work[G_ST] != 0.) return;
+  __shared__ double lds[4];
+  const GmresCells cells = gmres_cells(m);
+  const int j = gmres_column(work, m);
+  const double *h = work + (second ? cells.h2 : cells.h1);
+  double ww = 0;
+  NH_GS_ROWS(i) {
+    Pack<VW> wi = ld<VW>(w + i);
+    for (int k0 = 0; k0 <= j; k0 += C) {
+      const int nk = min(C, j + 1 - k0);
+      Pack<VW> vi[C];
+#pragma unroll
+      for (int c = 0; c < C; ++c)
+        if (c < nk) vi[c] = ld<VW>(V + (i64)(k0 + c) * n + i);
+#pragma unroll
+      for (int c = 0; c < C; ++c)
+        if (c < nk)
+#pragma unroll
+          for (int e = 0; e < VW; ++e) wi.v[e] -= h[k0 + c] * vi[c].v[e];
+    }
+    st<VW>(w + i, wi);
+    if (WW)
+#pragma unroll
+      for (int e = 0; e < VW; ++e) ww += wi.v[e] * wi.v[e];
+  }
+  if (WW) {
+    ww = block_sum(ww, lds);
+    if (threadIdx.x == 0) work[cells.wwp + blockIdx.x] = ww;
+  }
+}
+
+// the scalar work of step j, by one thread after the workgroup has summed the partials of w . w
+__global__ __launch_bounds__(WG) void k_gmres_scalars(int nparts, int m, double stop_rr, double *work) {
+  __shared__ double lds[4];
+  if (work[G_ST] != 0.) return;
+  const GmresCells c = gmres_cells(m);
+  const double ww = partial_sum(work + c.wwp, nparts, lds);
+  if (threadIdx.x) return;
+  const int j = gmres_column(work, m);
+  const double *h1 = work + c.h1, *h2 = work + c.h2;
+  double *cs = work + c.cs, *sn = work + c.sn, *g = work + c.g, *R = work + c.r + (i64)j * (m + 1);
+  double p = h1[0] + h2[0], col2 = p * p;
+  for (int k = 0; k < j; ++k) {  // the stored rotations, on (h_k, h_(k+1))
+    const double q = h1[k + 1] + h2[k + 1];
+    col2 += q * q;
+    R[k] = cs[k] * p + sn[k] * q;
+    p = cs[k] * q - sn[k] * p;
+  }
+  col2 += ww;
+  const bool vanish = !(ww > (GS_VANISH * GS_VANISH) * col2);
+  double st = ST_BAD, flag = 1., count = j;
+  if (finite(col2) && !(vanish && !(fabs(p) > GS_VANISH * sqrt(col2)))) {
+    const double q = vanish ? 0. : sqrt(ww);
+    const double d = fmax(hypot(p, q), fmax(fabs(p), q));  // (never below either: |sn| <= 1 and the estimate cannot rise, whatever hypot rounds to)
+    const double cj = p / d, sj = q / d, gj = g[j], gn = -sj * gj, rr = gn * gn;
+    if (finite(rr)) {
+      R[j] = d;
+      cs[j] = cj;
+      sn[j] = sj;
+      g[j] = cj * gj;
+      g[j + 1] = gn;
+      work[G_RR] = rr;
+      work[G_HN] = q;
+      count = j + 1;
+      flag = vanish ? 1. : 0.;
+      st = vanish || rr <= stop_rr ? ST_DONE : j + 1 >= m ? ST_FULL : 0.;
+    }
+  }
+  work[G_FLAG] = flag;
+  work[G_COUNT] = count;
+  work[G_ST] = st;
+}
+
+// y = R^-1 g for the columns taken, by one workgroup: column by column from the last, every thread owning the entries it updates
+__global__ __launch_bounds__(WG) void k_gmres_solve(int m, double *work) {
+  const GmresCells c = gmres_cells(m);
+  const int count = max(0, min((int)work[G_COUNT], m));
+  double *y = work + c.y;
+  for (int i = threadIdx.x; i < count; i += WG) y[i] = work[c.g + i];
+  __syncthreads();
+  for (int k = count - 1; k >= 0; --k) {
+    const double *col = work + c.r + (i64)k * (m + 1);
+    if (threadIdx.x == 0) y[k] = y[k] / col[k];
+    __syncthreads();
+    const double yk = y[k];
+    for (int i = threadIdx.x; i < k; i += WG) y[i] -= col[i] * yk;
+    __syncthreads();
+  }
+}
+
+// x += dinv sum_k y[k] v_k, k ascending over the columns taken
+template <int C, int VW>
+__global__ __launch_bounds__(WG) void k_gmres_xupdate(i64 n, int m, const double *__restrict__ dinv, const double *__restrict__ V, double *__restrict__ x,
+                                                      const double *__restrict__ work) {
+  const int count = max(0, min((int)work[G_COUNT], m));
+  if (!count) return;
+  const double *y = work + gmres_cells(m).y;
+  NH_GS_ROWS(i) {
+    Pack<VW> s;
+#pragma unroll
+    for (int e = 0; e < VW; ++e) s.v[e] = 0;
+    for (int k0 = 0; k0 < count; k0 += C) {
+      const int nk = min(C, count - k0);
+      Pack<VW> vi[C];
+#pragma unroll
+      for (int c = 0; c < C; ++c)
+        if (c < nk) vi[c] = ld<VW>(V + (i64)(k0 + c) * n + i);
+#pragma unroll
+      for (int c = 0; c < C; ++c)
+        if (c < nk)
+#pragma unroll
+          for (int e = 0; e < VW; ++e) s.v[e] += y[k0 + c] * vi[c].v[e];
+    }
+    Pack<VW> xi = ld<VW>(x + i);
+    if (dinv) {
+      const Pack<VW> d = ld<VW>(dinv + i);
+#pragma unroll
+      for (int e = 0; e < VW; ++e) xi.v[e] += d.v[e] * s.v[e];
+    } else
+#pragma unroll
+      for (int e = 0; e < VW; ++e) xi.v[e] += s.v[e];
+    st<VW>(x + i, xi);
+  }
+}
+#undef NH_GS_ROWS
+
 bool lanes_ok(int lanes) { return lanes >= 0 && lanes <= 64 && (lanes & (lanes - 1)) == 0; }
 
 int check_csr(const char *who, const nh_csr *A) {
@@ -422,7 +739,8 @@ int check_csr(const char *who, const nh_csr *A) {
 unsigned spmv_grid(i64 nrows, int L) { return (unsigned)std::min<i64>((nrows + WG / L - 1) / (WG / L), SPMV_MAX_WGS); }
 unsigned vec_grid(i64 n) { return (unsigned)std::min<i64>((n + WG - 1) / WG, VEC_MAX_WGS); }
 
-// what a product leaves besides y: nothing (partial == NULL), the partials of x . y (w == NULL), or those of w . y and y . y
+// what a product leaves besides y: nothing (partial == NULL), the partials of x . y (w == NULL), or those of w . y and y . y; with a skip cell and no
+// partials the plain product, not done when the cell is set
 struct Epilogue {
   double *partial = nullptr;
   const double *w = nullptr;
@@ -439,6 +757,9 @@ void launch_lanes(const nh_csr *A, const Idx *col, double alpha, const double *x
                        e.partial2, e.skip);
   else if (e.partial)
     hipLaunchKernelGGL((k_csr_spmv<L, Idx, 1>), grid, dim3(WG), 0, s, (i64)A->nrows, (const i64 *)A->rowptr_dev, col, A->values_dev, x, alpha, beta, b, mask, y, e.partial, e.w,
+                       e.partial2, e.skip);
+  else if (e.skip)
+    hipLaunchKernelGGL((k_csr_spmv<L, Idx, 3>), grid, dim3(WG), 0, s, (i64)A->nrows, (const i64 *)A->rowptr_dev, col, A->values_dev, x, alpha, beta, b, mask, y, e.partial, e.w,
                        e.partial2, e.skip);
   else
     hipLaunchKernelGGL((k_csr_spmv<L, Idx, 0>), grid, dim3(WG), 0, s, (i64)A->nrows, (const i64 *)A->rowptr_dev, col, A->values_dev, x, alpha, beta, b, mask, y, e.partial, e.w,
@@ -487,6 +808,44 @@ void launch_support(int L, const nh_csr *A, const Idx *col, double tol, unsigned
     NH_SUPPORT(64)
   }
 #undef NH_SUPPORT
+}
+
+// the Gram-Schmidt kernels take two doubles per load when every vector of V starts on a 16-byte boundary; they stride from the row count of the other vector kernels on
+bool gs_pairs(i64 n, std::initializer_list<const void *> vectors) {
+  if (n & 1) return false;
+  for (const void *p : vectors)
+    if ((uintptr_t)p & 15) return false;
+  return true;
+}
+unsigned gs_grid(i64 n, int vw) { return (unsigned)std::min<i64>((n + WG * vw - 1) / (WG * vw), VEC_MAX_WGS / vw); }
+
+// niter Arnoldi steps: nine launches each
+template <int VW>
+int gmres_steps(const nh_csr *B, const unsigned char *rowmask, const double *dinv, double *V, double *z, double *w, double *work, int m, double stop_rr, int niter,
+                hipStream_t s) {
+  const i64 n = B->nrows;
+  const dim3 grid(gs_grid(n, VW)), block(WG), sums((unsigned)std::min(m, 1024));
+  Epilogue e;
+  e.skip = work + G_ST;
+  for (int it = 0; it < niter; ++it) {
+    if (int rc = spmv(B, 1., z, 0., nullptr, rowmask, w, e, s)) return rc;
+    for (int second = 0; second < 2; ++second) {
+      hipLaunchKernelGGL((k_gmres_dots<GS_CHUNK, VW>), grid, block, 0, s, n, m, (const double *)V, (const double *)w, work);
+      NH_LAUNCH_CHECK();
+      hipLaunchKernelGGL(k_gmres_dots_sum, sums, block, 0, s, (int)grid.x, m, second, work);
+      NH_LAUNCH_CHECK();
+      if (second)
+        hipLaunchKernelGGL((k_gmres_axpy<GS_CHUNK, VW, true>), grid, block, 0, s, n, m, second, (const double *)V, w, work);
+      else
+        hipLaunchKernelGGL((k_gmres_axpy<GS_CHUNK, VW, false>), grid, block, 0, s, n, m, second, (const double *)V, w, work);
+      NH_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_gmres_scalars, dim3(1), block, 0, s, (int)grid.x, m, stop_rr, work);
+    NH_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_gmres_normalize<VW>, grid, block, 0, s, n, m, dinv, (const double *)w, V, z, (const double *)work);
+    NH_LAUNCH_CHECK();
+  }
+  return NH_OK;
 }
 
 }  // namespace
@@ -663,6 +1022,68 @@ int nh_bicgstab_iterate(const nh_csr *A, const unsigned char *rowmask_dev, const
     hipLaunchKernelGGL(k_bicgstab_direction, dim3(grid), dim3(WG), 0, s, n, (int)grid, stop_rr, work_dev, dinv_dev, (const double *)r_dev, (const double *)v_dev, p_dev, phat_dev);
     NH_LAUNCH_CHECK();
   }
+  return NH_OK;
+}
+
+int64_t nh_gmres_work_doubles(int restart) {
+  if (restart < 1) {
+    nh_set_error("nh_gmres_work_doubles: restart must be at least 1 (got %d)", restart);
+    return -1;
+  }
+  return gmres_cells(restart).end;
+}
+
+int nh_gmres_init(int64_t n, int restart, const double *dinv_dev, const double *r_dev, double *V_dev, double *z_dev, double *work_dev, void *stream) {
+  NH_REQUIRE(n >= 0, "nh_gmres_init: negative size");
+  NH_REQUIRE(restart >= 1, "nh_gmres_init: restart must be at least 1 (got %d)", restart);
+  NH_REQUIRE(work_dev && (!n || (r_dev && V_dev && z_dev)), "nh_gmres_init: NULL vector");
+  hipStream_t s = nh_stream(stream);
+  const unsigned grid = vec_grid(n);
+  if (n) {
+    hipLaunchKernelGGL(k_gmres_norm, dim3(grid), dim3(WG), 0, s, (i64)n, restart, r_dev, work_dev);
+    NH_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_gmres_init_scalars, dim3(1), dim3(WG), 0, s, (int)grid, restart, work_dev);
+  NH_LAUNCH_CHECK();
+  if (n) {
+    if (gs_pairs(n, {dinv_dev, r_dev, V_dev, z_dev}))
+      hipLaunchKernelGGL(k_gmres_normalize<2>, dim3(gs_grid(n, 2)), dim3(WG), 0, s, (i64)n, restart, dinv_dev, r_dev, V_dev, z_dev, (const double *)work_dev);
+    else
+      hipLaunchKernelGGL(k_gmres_normalize<1>, dim3(gs_grid(n, 1)), dim3(WG), 0, s, (i64)n, restart, dinv_dev, r_dev, V_dev, z_dev, (const double *)work_dev);
+    NH_LAUNCH_CHECK();
+  }
+  return NH_OK;
+}
+
+int nh_gmres_iterate(const nh_csr *A, const unsigned char *rowmask_dev, const double *dinv_dev, double *V_dev, double *z_dev, double *w_dev, double *work_dev, int restart,
+                     double stop_rr, int niter, void *stream) {
+  if (int rc = check_csr("nh_gmres_iterate", A)) return rc;
+  NH_REQUIRE(A->nrows == A->ncols, "nh_gmres_iterate: the matrix must be square (got %lld x %lld)", (long long)A->nrows, (long long)A->ncols);
+  NH_REQUIRE(restart >= 1, "nh_gmres_iterate: restart must be at least 1 (got %d)", restart);
+  NH_REQUIRE(niter >= 0, "nh_gmres_iterate: negative iteration count");
+  NH_REQUIRE(stop_rr >= 0., "nh_gmres_iterate: the bound on r . r must not be negative");
+  NH_REQUIRE(work_dev && (!A->nrows || (V_dev && z_dev && w_dev)), "nh_gmres_iterate: NULL vector");
+  if (!A->nrows) return NH_OK;
+  nh_csr B = *A;
+  B.lanes = A->lanes ? A->lanes : nh_csr_lanes(A->nrows, A->nnz);
+  if (gs_pairs(A->nrows, {dinv_dev, V_dev, z_dev, w_dev}))
+    return gmres_steps<2>(&B, rowmask_dev, dinv_dev, V_dev, z_dev, w_dev, work_dev, restart, stop_rr, niter, nh_stream(stream));
+  return gmres_steps<1>(&B, rowmask_dev, dinv_dev, V_dev, z_dev, w_dev, work_dev, restart, stop_rr, niter, nh_stream(stream));
+}
+
+int nh_gmres_update(int64_t n, int restart, const double *dinv_dev, const double *V_dev, double *x_dev, double *work_dev, void *stream) {
+  NH_REQUIRE(n >= 0, "nh_gmres_update: negative size");
+  NH_REQUIRE(restart >= 1, "nh_gmres_update: restart must be at least 1 (got %d)", restart);
+  NH_REQUIRE(work_dev && (!n || (V_dev && x_dev)), "nh_gmres_update: NULL vector");
+  if (!n) return NH_OK;
+  hipStream_t s = nh_stream(stream);
+  hipLaunchKernelGGL(k_gmres_solve, dim3(1), dim3(WG), 0, s, restart, work_dev);
+  NH_LAUNCH_CHECK();
+  if (gs_pairs(n, {dinv_dev, V_dev, x_dev}))
+    hipLaunchKernelGGL((k_gmres_xupdate<GS_CHUNK, 2>), dim3(gs_grid(n, 2)), dim3(WG), 0, s, (i64)n, restart, dinv_dev, V_dev, x_dev, (const double *)work_dev);
+  else
+    hipLaunchKernelGGL((k_gmres_xupdate<GS_CHUNK, 1>), dim3(gs_grid(n, 1)), dim3(WG), 0, s, (i64)n, restart, dinv_dev, V_dev, x_dev, (const double *)work_dev);
+  NH_LAUNCH_CHECK();
   return NH_OK;
 }
 

@@ -909,3 +909,32 @@ def bicgstab_iterate(values, rowptr, colidx, ncols, *, rowmask, dinv, x, r, rhat
     _lib.call('nh_bicgstab_iterate', ctypes.byref(_csr(values, rowptr, colidx, ncols, col32, lanes)), device.ptr(rowmask), device.ptr(dinv), device.ptr(x), device.ptr(r),
               device.ptr(rhat), device.ptr(p), device.ptr(v), device.ptr(s), device.ptr(t), device.ptr(phat), device.ptr(shat), device.ptr(work), float(stop_rr), int(niter),
               device.stream())
+
+
+GMRES_CHUNK = 8  # GS_CHUNK of nh_csr.hip: basis vectors the Gram-Schmidt kernels take per pass over w
+
+
+def gmres_work(restart):
+    '''the work array of a GMRES cycle of up to `restart` steps (nh_gmres_work_doubles): [0] = the squared residual norm of the least-squares problem (after
+    `gmres_init`: r . r), [1] = 1. once a direction vanished or was not finite, [2] = Arnoldi steps since `gmres_init`'''
+    size = _lib.load().nh_gmres_work_doubles(int(restart))
+    if size < 0:
+        _lib.check(-1)
+    return device.empty(size, 'float64')
+
+
+def gmres_init(dinv, r, V, z, work, *, restart):
+    '''start a cycle from the residual r: v_0 = r / |r|, z = dinv v_0, the cells cleared (nh_gmres_init); `V` holds restart + 1 vectors'''
+    _lib.call('nh_gmres_init', r.numel(), int(restart), device.ptr(dinv), device.ptr(r), device.ptr(V), device.ptr(z), device.ptr(work), device.stream())
+
+
+def gmres_iterate(values, rowptr, colidx, ncols, *, rowmask, dinv, V, z, w, work, restart, stop_rr, niter, col32=None, lanes=0):
+    '''enqueue `niter` Arnoldi steps (nh_gmres_iterate): nine launches each, nothing read back; they stop moving once the estimate is within stop_rr, the
+    cycle is full or a direction has vanished'''
+    _lib.call('nh_gmres_iterate', ctypes.byref(_csr(values, rowptr, colidx, ncols, col32, lanes)), device.ptr(rowmask), device.ptr(dinv), device.ptr(V), device.ptr(z),
+              device.ptr(w), device.ptr(work), int(restart), float(stop_rr), int(niter), device.stream())
+
+
+def gmres_update(dinv, V, x, work, *, restart):
+    '''x += dinv V y for the columns the cycle has taken (nh_gmres_update)'''
+    _lib.call('nh_gmres_update', x.numel(), int(restart), device.ptr(dinv), device.ptr(V), device.ptr(x), device.ptr(work), device.stream())

@@ -8,14 +8,14 @@ conditions) is the reference's.
 
 Two backends.  'scipy' (the default; 'auto' means the same) wraps the host copy
 of the triplet in a ``ScipyMatrix`` with a direct solver.  'hip' keeps the
-triplet in HBM as a ``HipMatrix``: products, the diagonal and two Jacobi-
+triplet in HBM as a ``HipMatrix``: products, the diagonal and three Jacobi-
 preconditioned Krylov solves -- conjugate gradients ('cg') for symmetric
-positive definite systems, BiCGStab ('bicgstab') for any square matrix --
-run on the device (nh_csr.hip); ``function.eval(function.as_matrix(K))`` builds
+positive definite systems, BiCGStab ('bicgstab') and restarted GMRES
+('fgmres') for any square matrix -- run on the device (nh_csr.hip); ``function.eval(function.as_matrix(K))`` builds
 one without the triplet ever visiting the host, and so does ``solver.System``
 under this backend (``assemble_device``).  What a ``HipMatrix`` does
 through scipy and a re-upload -- ``submatrix``, ``T``, every solver other than
-'cg' and 'bicgstab', sums of matrices with different patterns -- says so in its
+'cg', 'bicgstab' and 'fgmres', sums of matrices with different patterns -- says so in its
 docstring.
 '''
 
@@ -169,9 +169,9 @@ class HipMatrix:
     (12 instead of 16 bytes per entry; matrices with more than 2^31 - 1 columns keep the int64 indices).
 
     On the device: products (nh_csr_spmv), the diagonal, `rowsupp` / `colsupp` (nh_csr_support), scalar multiples, sums of matrices that share their index tensors, `solve(solver='cg')`, a
-    Jacobi-preconditioned conjugate-gradient iteration for SYMMETRIC POSITIVE DEFINITE systems, and `solve(solver='bicgstab')`, a Jacobi-preconditioned
-    BiCGStab iteration for ANY square system (nonsymmetric, indefinite); both with ONE right-hand side.  `iterations` is the iteration count of the last device
-    solve.  Through scipy and PCIe (export, host operation, re-upload): `submatrix`, `T`, sums of matrices with different patterns, every other solver.'''
+    Jacobi-preconditioned conjugate-gradient iteration for SYMMETRIC POSITIVE DEFINITE systems, and for ANY square system (nonsymmetric, indefinite)
+    `solve(solver='bicgstab')`, a Jacobi-preconditioned BiCGStab iteration, and `solve(solver='fgmres')`, Jacobi-preconditioned restarted GMRES, whose residual
+    norm never rises within a cycle; all with ONE right-hand side.  `iterations` is the iteration count of the last device solve.  Through scipy and PCIe (export, host operation, re-upload): `submatrix`, `T`, sums of matrices with different patterns, every other solver.'''
 
     def __init__(self, values, rowptr, colidx, ncols, *, validate=True):
         self._ncols = int(ncols)
@@ -335,7 +335,7 @@ class HipMatrix:
 
     # -- solve
 
-    def solve(self, rhs=None, *, lhs0=None, constrain=None, solver='cg', atol=0., rtol=0., precon='diag', maxiter=None, check=16, **solverargs):
+    def solve(self, rhs=None, *, lhs0=None, constrain=None, solver='cg', atol=0., rtol=0., precon='diag', maxiter=None, check=16, restart=30, **solverargs):
         '''Solve A x = rhs with constraints in the reference's convention (`constraints`; Matrix.solve, matrix/_base.py:100-176).
 
         solver='cg': conjugate gradients on the device for a SYMMETRIC POSITIVE DEFINITE matrix and ONE right-hand side.  No submatrix is formed: the free
@@ -352,6 +352,15 @@ class HipMatrix:
         breakdown of the recurrence (a vanishing rhat . r, rhat . v, t . t or omega) after progress restarts it from the true residual with a fresh shadow
         residual, the iterations counting on; a breakdown at the first step after a start raises MatrixError('bicgstab: breakdown').
 
+        solver='fgmres': right-preconditioned restarted GMRES on the device for ANY square matrix and ONE right-hand side (with the fixed Jacobi preconditioner
+        flexible and right-preconditioned GMRES are the same iteration; the reference's name for it is matrix/_mkl.py's), with the keywords, the row mask and
+        the bound of 'cg'.  A cycle starts from the true residual, takes up to `restart` Arnoldi steps (a keyword of this solver alone, the others ignore it; an integer of at least 1, clipped to the number of
+        free dofs; one product and two passes of classical Gram-Schmidt each) and ends with x += M^-1 V y; its residual norm, which the device knows from the
+        rotated right-hand side, never rises.  The cycle stops itself on the device, so `iterations`, the Arnoldi steps over all cycles, is exact whatever
+        `check` is, and `maxiter` counts the same.  When a new direction vanishes or is not finite the cycle ends there; if the true residual is then above the
+        bound without having fallen in that cycle (or in the
+        one after it, which may get a direction of the size of a rounding and no further) the solve raises MatrixError('fgmres: singular matrix').
+
         Any other `solver` is a PCIe path: the matrix is exported to a ScipyMatrix and solved there.
 
         Returns a numpy vector, or a device tensor if `rhs` was one.'''
@@ -366,7 +375,7 @@ class HipMatrix:
                 raise MatrixError('right-hand side shape does not match matrix shape')
         if nrows != ncols:
             raise MatrixError(f'constrained matrix is not square: {nrows}x{ncols}')
-        if solver not in ('cg', 'bicgstab'):
+        if solver not in ('cg', 'bicgstab', 'fgmres'):
             x = self._scipy().solve(_host(rhs), lhs0=_host(lhs0), constrain=_host(constrain), **solverargs)
             if on_device:
                 from . import device
@@ -376,9 +385,12 @@ class HipMatrix:
             raise MatrixError(f"solver {solver!r} needs a tolerance: pass atol or rtol (an iterative solve has no machine-precision mode)")
         if precon not in ('diag', None):
             raise MatrixError(f'invalid preconditioner {precon!r} for HipMatrix: \'diag\' or None')
+        if solver == 'fgmres' and not (isinstance(restart, (int, numpy.integer)) and not isinstance(restart, bool) and restart >= 1):
+            raise MatrixError(f'fgmres: restart must be an integer of at least 1, got {restart!r}')
         free, lhs = constraints(ncols, _host(constrain), _host(lhs0))
-        krylov = self._cg if solver == 'cg' else self._bicgstab
-        return krylov(rhs, free, lhs, atol, rtol, precon, int(free.sum()) if maxiter is None else int(maxiter), max(1, int(check)), on_device)
+        krylov = self._cg if solver == 'cg' else self._bicgstab if solver == 'bicgstab' else self._fgmres
+        args = (rhs, free, lhs, atol, rtol, precon, int(free.sum()) if maxiter is None else int(maxiter), max(1, int(check)), on_device)
+        return krylov(*args, int(restart)) if solver == 'fgmres' else krylov(*args)
 
     def solve_leniently(self, *args, **kwargs):
         '''`solve` that returns the vector reached instead of raising ToleranceNotReached'''
@@ -478,6 +490,46 @@ class HipMatrix:
                     raise MatrixError('bicgstab: non-finite residual')
                 if rr <= stop_rr:
                     break
+
+    def _fgmres(self, rhs, free, lhs, atol, rtol, precon, maxiter, check, on_device, restart):
+        from . import device, kernels
+        n = self.shape[0]
+        values, rowptr, colidx = self.triplet()
+        mask, x, b, dinv = self._krylov_setup(rhs, free, lhs, precon, on_device)
+        m = max(1, min(restart, int(free.sum())))  # (a Krylov space has no more dimensions than there are free dofs)
+        r, z, w = (device.empty(n, 'float64') for _ in range(3))
+        V = device.empty((m + 1) * n, 'float64')
+        work = kernels.gmres_work(m)
+        result = (lambda: x) if on_device else (lambda: device.to_host(x))
+        stop_rr, it, since, rr_start = None, 0, None, None  # since: cycles finished since one ended on a vanished direction (0: the last one did)
+        while True:  # a cycle: from the true residual
+            self.iterations = it
+            self.spmv(x, alpha=-1., beta=1., b=b, rowmask=mask, y=r)  # mask(rhs - A x)
+            kernels.gmres_init(dinv, r, V, z, work, restart=m)
+            rr = work[:1].item()
+            if stop_rr is None:
+                stop_rr = max(atol, rtol * rr ** .5) ** 2  # (the device compares its estimate with this number, and so does the host)
+            if not numpy.isfinite(rr):
+                raise MatrixError('fgmres: non-finite residual')
+            if rr <= stop_rr:
+                return result()
+            if since in (0, 1) and not rr < rr_start:
+                # A direction has vanished: the Krylov space of that start was exhausted, which for a nonsingular matrix means the update solved the system to
+                # rounding.  If that cycle got nowhere, or the next one on what rounding left of the residual (on diag(1, 0) it finds a direction of the size of
+                # a rounding in x, and no flag), the matrix is singular.  Later cycles that stagnate are restarted GMRES stagnating: they run to maxiter.
+                raise MatrixError('fgmres: singular matrix')
+            if it >= maxiter:
+                raise ToleranceNotReached(result())
+            start, rr_start = it, rr
+            while it < maxiter:
+                kernels.gmres_iterate(values, rowptr, colidx, self._ncols, rowmask=mask, dinv=dinv, V=V, z=z, w=w, work=work, restart=m, stop_rr=stop_rr,
+                                      niter=min(check, maxiter - it), col32=self._columns(), lanes=self.lanes)
+                est, flag, steps = work[:3].tolist()
+                self.iterations = it = start + int(steps)  # (the device counts the columns it took: exact, not a multiple of `check`)
+                if flag or est <= stop_rr or steps >= m:
+                    break
+            since = 0 if flag else None if since is None else since + 1
+            kernels.gmres_update(dinv, V, x, work, restart=m)
 
 
 class _HipBackend:

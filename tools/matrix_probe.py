@@ -9,10 +9,14 @@
   * for the nonsymmetric twin N = K + 0.5 (triu(K, 1) - tril(K, -1)), built on the device from the value tensor: the time of a BiCGStab iteration against
     two products of the same run and against its vector passes at the stream rate, iterations, wall time and true residual of a Jacobi-BiCGStab solve under
     the conditions of the CG solve, and (unless --no-host-solve) the route a user had before: device.to_host of the triplet, the free submatrix and
-    scipy.sparse.linalg.bicgstab with the same tolerance and Jacobi as a LinearOperator, timed once.
+    scipy.sparse.linalg.bicgstab with the same tolerance and Jacobi as a LinearOperator, timed once,
+  * for the same twin, restarted GMRES at restart 10, 30 and 100: the time of an Arnoldi step (the mean over a full cycle, whose step j reads j + 1 basis
+    vectors four times), the product's share of it and the share of everything else (the Gram-Schmidt kernels, the scalar kernel, the normalisation), the
+    model's bytes of that rest, (4 (j + 1) + c) 8 n per step with c = 2 ceil((j + 1) / 8) + 8 passes over w, z, dinv and the new basis vector, over its time as a
+    fraction of 8 TB/s, and steps, wall time and true residual of a Jacobi-GMRES solve under the conditions of the BiCGStab solve.
 
-Usage: python tools/matrix_probe.py [--matrices poisson128,elasticity96,bilinear2048,p2vector32] [--scale 1.0] [--out FILE]
-(--scale shrinks every mesh for a quick look).  Not run by any test.'''
+Usage: python tools/matrix_probe.py [--matrices poisson128,elasticity96,bilinear2048,p2vector32] [--scale 1.0] [--sections spmv,cg,bicgstab,fgmres] [--out FILE]
+(--scale shrinks every mesh for a quick look; --sections leaves parts out).  Not run by any test.'''
 import argparse
 import json
 import os
@@ -124,6 +128,28 @@ def probe(name, args):
         torch_fn = None
         info['torch_csr'] = f'unavailable: {type(e).__name__}: {e}'
 
+    free = ~held
+    mask = device.to_dev(free, 'uint8')
+    rhs = numpy.random.default_rng(2).normal(size=nrows)
+    rhs_dev = device.to_dev(rhs, 'float64')
+    res0 = torch.where(mask != 0, rhs_dev, torch.zeros_like(rhs_dev))
+    if 'spmv' in args.sections:
+        probe_spmv(A, x, y, nbytes, torch_fn, info, args)
+    if 'cg' in args.sections:
+        probe_cg(A, free, mask, rhs_dev, res0, info, args)
+    if 'bicgstab' in args.sections:
+        info['bicgstab'] = probe_bicgstab(A, free, mask, rhs_dev, res0, args)
+    if 'fgmres' in args.sections:
+        info['fgmres'] = probe_fgmres(A, free, mask, rhs_dev, res0, args)
+    return info
+
+
+def probe_spmv(A, x, y, nbytes, torch_fn, info, args):
+    '''the product for every lane count, torch's, the int64 columns, and the host's'''
+    import scipy.sparse
+    from nutils_amd import device, kernels
+    values, rowptr, colidx = A.triplet()
+    nrows, ncols = A.shape
     lanes = sorted(set(LANES) | {A.lanes})
     fns = [(lambda L=L: A.spmv(x, y=y, lanes=L)) for L in lanes]
     if torch_fn:
@@ -157,9 +183,14 @@ def probe(name, args):
     info['scipy_matvec_ms'] = (time.perf_counter() - t0) / 3 * 1e3
     del S, hv, hrp, hci
 
-    # CG: time per iteration, the product's share, a solve
-    free = ~held
-    mask = device.to_dev(free, 'uint8')
+
+def probe_cg(A, free, mask, rhs_dev, res0, info, args):
+    '''CG: time per iteration, the product's share, a solve'''
+    import torch
+    from nutils_amd import device, kernels, matrix
+    values, rowptr, colidx = A.triplet()
+    nrows, ncols = A.shape
+    held = ~free
     dinv = (1. / A._diagonal_dev()).masked_fill(mask == 0, 0.)
     r = torch.from_numpy(numpy.random.default_rng(1).normal(size=nrows) * free).cuda()
     xs, p, q = torch.zeros_like(r), torch.empty_like(r), torch.empty_like(r)
@@ -170,8 +201,6 @@ def probe(name, args):
     it, mv = windows([step, masked], args.window)
     info['cg_iteration'] = stats([t / 10 for t in it])
     info['cg_spmv_share'] = float(numpy.median(mv)) / info['cg_iteration']['us'] * 1e6
-    rhs = numpy.random.default_rng(2).normal(size=nrows)
-    rhs_dev = device.to_dev(rhs, 'float64')
     device.synchronize()
     t0 = time.perf_counter()
     try:
@@ -182,13 +211,18 @@ def probe(name, args):
         info['solve'] = dict(converged=False)
     device.synchronize()
     info['solve'].update(wall_ms=(time.perf_counter() - t0) * 1e3, iterations=A.cg_iterations)
-    res0 = torch.where(mask != 0, rhs_dev, torch.zeros_like(rhs_dev))
     info['solve']['true_relative_residual'] = float(A.spmv(sol, alpha=-1., beta=1., b=rhs_dev, rowmask=mask).norm() / res0.norm())
-    info['bicgstab'] = probe_bicgstab(A, free, mask, rhs_dev, res0, args)
-    return info
 
 
 BICGSTAB_STEPS = 20
+
+
+def nonsymmetric_twin(A):
+    '''N = K + 0.5 (triu(K, 1) - tril(K, -1)) on the index tensors of A (set-up, not timed)'''
+    import torch
+    values, rowptr, colidx = A.triplet()
+    rows = torch.repeat_interleave(torch.arange(A.shape[0], device=values.device), rowptr[1:] - rowptr[:-1])
+    return A._with_values(values * (1 + .5 * torch.sign(colidx - rows)))
 
 
 def probe_bicgstab(A, free, mask, rhs_dev, res0, args):
@@ -199,9 +233,7 @@ def probe_bicgstab(A, free, mask, rhs_dev, res0, args):
     from nutils_amd import device, kernels, matrix
     values, rowptr, colidx = A.triplet()
     nrows, ncols = A.shape
-    rows = torch.repeat_interleave(torch.arange(nrows, device=values.device), rowptr[1:] - rowptr[:-1])
-    N = A._with_values(values * (1 + .5 * torch.sign(colidx - rows)))  # set-up, not timed
-    del rows
+    N = nonsymmetric_twin(A)
     nvalues = N.triplet()[0]
     out = {}
     dinv = (1. / N._diagonal_dev()).masked_fill(mask == 0, 0.)
@@ -273,6 +305,63 @@ def probe_bicgstab(A, free, mask, rhs_dev, res0, args):
     return out
 
 
+RESTARTS = (10, 30, 100)
+
+
+def probe_fgmres(A, free, mask, rhs_dev, res0, args):
+    '''the nonsymmetric twin of A under restarted GMRES: the time of an Arnoldi step and where it goes, and a solve, per restart'''
+    import torch
+    from nutils_amd import device, kernels, matrix
+    _, rowptr, colidx = A.triplet()
+    nrows, ncols = A.shape
+    N = nonsymmetric_twin(A)
+    nvalues = N.triplet()[0]
+    dinv = (1. / N._diagonal_dev()).masked_fill(mask == 0, 0.)
+    r0 = torch.from_numpy(numpy.random.default_rng(1).normal(size=nrows) * free).cuda()
+    z, w = torch.zeros_like(r0), torch.zeros_like(r0)
+    out = {}
+    for m in RESTARTS:
+        V = torch.zeros((m + 1) * nrows, dtype=torch.float64, device='cuda')
+        work = kernels.gmres_work(m)
+        start = lambda: kernels.gmres_init(dinv, r0, V, z, work, restart=m)
+
+        def cycle():  # a whole cycle from the same residual: step j = 0 .. m - 1, none of them stopped (the bound is zero)
+            start()
+            kernels.gmres_iterate(nvalues, rowptr, colidx, ncols, rowmask=mask, dinv=dinv, V=V, z=z, w=w, work=work, restart=m, stop_rr=0., niter=m, col32=A._columns(),
+                                  lanes=A.lanes)
+
+        masked = lambda: N.spmv(z, y=w, rowmask=mask)
+        t_cycle, t_start, t_mv = windows([cycle, start, masked], args.window)
+        cycle()
+        est, flag, count = work[:3].tolist()
+        res = dict(steps_per_call=count, flag=flag)  # (m and 0, or the time below is not that of a step)
+        res['step'] = stats([(a - b) / m for a, b in zip(t_cycle, t_start)])
+        res['masked_spmv'] = stats(t_mv)
+        res['spmv_share'] = res['masked_spmv']['us'] / res['step']['us']
+        rest_us = res['step']['us'] - res['masked_spmv']['us']
+        res['rest_share'] = rest_us / res['step']['us']  # the Gram-Schmidt kernels, with the scalar kernel, the normalisation and the gaps between nine launches
+        passes = [4 * (j + 1) + 2 * -(-(j + 1) // kernels.GMRES_CHUNK) + 8 for j in range(m)]
+        res['model_passes_per_step'] = sum(passes) / m
+        res['rest_frac_8TBs'] = sum(passes) / m * 8 * nrows / (rest_us * 1e-6) / 8e12 if rest_us > 0 else None
+        del V, work
+        device.synchronize()
+        t0 = time.perf_counter()
+        try:
+            sol = N.solve(rhs_dev, constrain=~free, solver='fgmres', restart=m, rtol=1e-8, maxiter=args.maxiter)
+            res['solve'] = dict(converged=True)
+        except matrix.ToleranceNotReached as e:
+            sol = e.best
+            res['solve'] = dict(converged=False)
+        device.synchronize()
+        res['solve'].update(wall_ms=(time.perf_counter() - t0) * 1e3, iterations=N.iterations)
+        res['solve']['true_relative_residual'] = float(N.spmv(sol, alpha=-1., beta=1., b=rhs_dev, rowmask=mask).norm() / res0.norm())
+        res['solve']['ms_per_step'] = res['solve']['wall_ms'] / max(1, N.iterations)
+        del sol
+        torch.cuda.empty_cache()
+        out[str(m)] = res
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--matrices', default='poisson128,elasticity96,bilinear2048,p2vector32')
@@ -280,8 +369,10 @@ def main():
     ap.add_argument('--window', type=float, default=.3)
     ap.add_argument('--maxiter', type=int, default=20000)
     ap.add_argument('--no-host-solve', action='store_true', help='skip the host BiCGStab of the nonsymmetric twin (minutes for the large matrices)')
+    ap.add_argument('--sections', default='spmv,cg,bicgstab,fgmres', help='the parts of the probe to run')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
+    args.sections = args.sections.split(',')
     import torch
     out = open(args.out, 'a') if args.out else None
     for name in args.matrices.split(','):
