@@ -758,6 +758,50 @@ int nh_gmres_iterate(const nh_csr *A, const unsigned char *rowmask_dev, const do
                      double stop_rr, int niter, void *stream);
 int nh_gmres_update(int64_t n, int restart, const double *dinv_dev, const double *V_dev, double *x_dev, double *work_dev, void *stream);
 
+/* ---- smoothed-aggregation AMG as the preconditioner of the CG solve (nh_amg.hip) ----------------------
+ * The symbolic phase of the setup (aggregates, the patterns of P, R = P^T and A_c = R A P, and for each of the products A T, A P, R (A P) an
+ * expand-sort-compress plan) is the caller's; these entries read value arrays.  By the rules above: nothing atomic, every sum in a fixed order, launch
+ * geometry a function of sizes only, repeated calls bit-identical, argument errors NH_EINVAL before a launch, empty sizes no launch.
+ * nh_segment_dot: out[s] = sum of a[ia[k]] * b[ib[k]] over k = ptr[s] .. ptr[s + 1] - 1, s < nseg; b_dev NULL: the plain segment sum of a[ia[k]].  ptr int64
+ * [nseg + 1], ia / ib int32 [nprod], nprod = ptr[nseg].  Lanes per segment follow from the mean segment length by the rule of nh_csr_lanes.
+ * nh_csr_jacobi: y = x + w (b - A x) on the rows the mask keeps, 0 on the others, in one launch; y must not be x.
+ * nh_amg is a hierarchy made of level descriptions; like nh_csr it holds views and owns no device memory, and every vector of a description is the caller's
+ * to allocate and to keep.  Level l < nlevels - 1 has kind NH_AMG_COARSEN: A (its matrix), rowmask_dev (level 0 only; NULL: all rows), w_dev = omega / diag
+ * (0 on masked rows), P [n x n_c] and R = P^T [n_c x n] as CSR views of their own, sweeps >= 1, t_dev and r_dev: n doubles each; for l > 0 also b_dev and x_dev.
+ * The last level is NH_AMG_DENSE -- Ainv_dev [ndense x ndense] row-major, ndense <= 1024; idx_dev int32 [ndense] lists the rows it acts on when ndense is
+ * less than the rows of A (a masked level 0), whose other rows get 0 -- or NH_AMG_DIAGONAL, z = w b with w_dev = 1 / diag.
+ * nh_amg_apply enqueues z = M r, one V(sweeps, sweeps) cycle from level 0, and returns: the first sweep x = w b, further ones x += w (b - A x), then
+ * r = b - A x, b_c = R r, the cycle below, x += P x_c, and `sweeps` sweeps more.  With one sweep that is five launches a level.  r_dev and z_dev: n doubles, distinct.
+ * nh_pcg_*: conjugate gradients with that cycle as the preconditioner.  An iteration: q = mask(A p) with the partials of p . q; alpha, x += alpha p,
+ * r -= alpha q, partials of r . r; z = M r; partials of r . z; beta, p = z + beta p.  work_dev: nh_pcg_work_doubles() doubles; work[0 .. 2] are r . r, the
+ * breakdown flag and the stopping bound with the meaning they have in nh_cg_*: once r . r <= work[2] no iteration moves x, r or p or raises the flag; a
+ * p . q or r . z that is not a positive finite number while r . r > work[2] raises it and freezes the vectors.  nh_pcg_init forms z = M r, p = z and the
+ * first r . z, r . r from a given r, and clears flag and bound. */
+typedef struct nh_amg nh_amg;
+enum { NH_AMG_COARSEN = 0, NH_AMG_DENSE = 1, NH_AMG_DIAGONAL = 2 };
+typedef struct {
+  nh_csr A;
+  const unsigned char *rowmask_dev;
+  const double *w_dev;
+  nh_csr P, R;
+  double *b_dev, *x_dev, *t_dev, *r_dev;
+  int kind, sweeps;
+  int64_t ndense;
+  const double *Ainv_dev;
+  const int32_t *idx_dev;
+} nh_amg_level;
+
+int nh_segment_dot(int64_t nseg, const int64_t *ptr_dev, const int32_t *ia_dev, const int32_t *ib_dev, const double *a_dev, const double *b_dev, int64_t nprod,
+                   double *out_dev, void *stream);
+int nh_csr_jacobi(const nh_csr *A, const double *x_dev, const double *w_dev, const double *b_dev, const unsigned char *rowmask_dev, double *y_dev, void *stream);
+int nh_amg_create(const nh_amg_level *levels, int nlevels, nh_amg **out);
+int nh_amg_free(nh_amg *amg);
+int nh_amg_apply(const nh_amg *amg, const double *r_dev, double *z_dev, void *stream);
+int64_t nh_pcg_work_doubles(void);
+int nh_pcg_init(int64_t n, const nh_amg *amg, const double *r_dev, double *z_dev, double *p_dev, double *work_dev, void *stream);
+int nh_pcg_iterate(const nh_csr *A, const unsigned char *rowmask_dev, const nh_amg *amg, double *x_dev, double *r_dev, double *z_dev, double *p_dev, double *q_dev,
+                   double *work_dev, int niter, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

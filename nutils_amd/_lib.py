@@ -127,6 +127,13 @@ class Csr(ctypes.Structure):
                 ('lanes', ctypes.c_int)]
 
 
+class AmgLevel(ctypes.Structure):
+    _fields_ = [('A', Csr), ('rowmask_dev', vp), ('w_dev', vp), ('P', Csr), ('R', Csr), ('b_dev', vp), ('x_dev', vp), ('t_dev', vp), ('r_dev', vp),
+                ('kind', ctypes.c_int), ('sweeps', ctypes.c_int), ('ndense', c_i64), ('Ainv_dev', vp), ('idx_dev', vp)]
+
+
+AMG_KINDS = {'coarsen': 0, 'dense': 1, 'diagonal': 2}
+
 GEOM_ISO = 1
 GEOM_BOX = 2
 GEOM_TAB = 3
@@ -210,6 +217,14 @@ SIGNATURES = {
     'nh_gmres_init': (ctypes.c_int, [c_i64, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
     'nh_gmres_iterate': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, vp]),
     'nh_gmres_update': (ctypes.c_int, [c_i64, ctypes.c_int, vp, vp, vp, vp, vp]),
+    'nh_segment_dot': (ctypes.c_int, [c_i64, vp, vp, vp, vp, vp, c_i64, vp, vp]),
+    'nh_csr_jacobi': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, vp, vp, vp, vp]),
+    'nh_amg_create': (ctypes.c_int, [ctypes.POINTER(AmgLevel), ctypes.c_int, ctypes.POINTER(vp)]),
+    'nh_amg_free': (ctypes.c_int, [vp]),
+    'nh_amg_apply': (ctypes.c_int, [vp, vp, vp, vp]),
+    'nh_pcg_work_doubles': (c_i64, []),
+    'nh_pcg_init': (ctypes.c_int, [c_i64, vp, vp, vp, vp, vp, vp]),
+    'nh_pcg_iterate': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int, vp]),
 }
 
 _lib = None

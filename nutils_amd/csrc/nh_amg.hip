@@ -1,0 +1,389 @@
+// Smoothed-aggregation algebraic multigrid as the preconditioner of the device CG solve: the numeric phase of the setup, the V-cycle, and a conjugate-gradient
+// iteration whose preconditioner is that cycle.  The symbolic phase (aggregates, patterns, expand-sort-compress plans) is torch plumbing (nutils_amd/amg.py);
+// what is here reads value arrays.  The rules are those of nh_csr.hip: nothing atomic, every sum in a fixed order, launch geometry a function of sizes only,
+// repeated calls bit-identical.
+//
+//   * k_segment_dot<L>: out[s] = sum_k a[ia[k]] b[ib[k]] over k = ptr[s] .. ptr[s+1] - 1 (b == NULL: a plain segment sum) -- a sparse product whose
+//     products have been listed and sorted by output entry beforehand.  L lanes own a segment, consecutive lane groups take consecutive segments (so a
+//     wave reads one contiguous span of the index arrays), segments longer than L are walked in strides of L and folded with __shfl_xor: the mapping
+//     of k_csr_spmv.  It evaluates A T, A P and R (A P) of every level.
+//   * k_jacobi<L, Idx>: y = x + w (b - A x) on the rows the mask keeps, 0 elsewhere, in one launch (k_csr_spmv with another epilogue; y != x).
+//   * k_scale: y = w b, the sweep that starts from zero, and the solve of a diagonal terminal level.
+//   * k_dense: z = Ainv b for the coarsest level, one workgroup, a wave per row, lanes over the columns.
+//   * the cycle (amg_cycle) is a host loop over the level descriptions that enqueues those kernels and nh_csr_spmv (residual, restriction,
+//     prolongate-and-add); with one sweep that is five launches per level and one for the coarsest.
+//   * k_pcg_*: CG with z = M r handed in.  An iteration: q = mask(A p) with the partials of p . q (the DOT = 1 product of nh_csr.hip); update (alpha, x,
+//     r, partials of r . r); the cycle; partials of r . z; direction (beta, p = z + beta p).  The cell discipline is that of k_cg_update / k_cg_direction.
+#include "nh_common.h"
+#include <algorithm>
+#include <climits>
+#include <cstdint>
+#include <new>
+#include <vector>
+
+struct nh_amg {
+  std::vector<nh_amg_level> levels;
+};
+
+namespace {
+
+#include "nh_krylov.inc"  // WG, the grid caps, block_sum, partial_sum, check_csr, spmv_grid, vec_grid, and the cells W_RR, W_FLAG_B, W_STOP: shared with nh_csr.hip
+
+constexpr int DENSE_WG = 1024;
+
+// the other cells of the work array of nh_pcg_* (the first three are W_RR, W_FLAG_B, W_STOP, as in nh_cg_*)
+enum { P_FLAG_A = 3, P_RZ_A = 4, P_RZ_B = 5, P_PQ = 8, P_RZP = P_PQ + SPMV_MAX_WGS, P_RRP = P_RZP + VEC_MAX_WGS, P_END = P_RRP + VEC_MAX_WGS };
+
+template <int L>
+__global__ __launch_bounds__(WG) void k_segment_dot(i64 nseg, const i64 *__restrict__ ptr, const int32_t *__restrict__ ia, const int32_t *__restrict__ ib,
+                                                    const double *__restrict__ a, const double *__restrict__ b, double *__restrict__ out) {
+  constexpr int G = WG / L;
+  const int lane = threadIdx.x & (L - 1);
+  for (i64 base = (i64)blockIdx.x * G; base < nseg; base += (i64)gridDim.x * G) {  // (uniform trip count: every lane takes part in the shuffles)
+    const i64 seg = base + threadIdx.x / L;
+    const bool live = seg < nseg;
+    double s = 0;
+    if (live) {
+      const i64 k1 = ptr[seg + 1];
+      if (b) {
+#pragma unroll 2
+        for (i64 k = ptr[seg] + lane; k < k1; k += L) s += a[ia[k]] * b[ib[k]];
+      } else {
+#pragma unroll 2
+        for (i64 k = ptr[seg] + lane; k < k1; k += L) s += a[ia[k]];
+      }
+    }
+#pragma unroll
+    for (int o = L >> 1; o; o >>= 1) s += __shfl_xor(s, o, L);
+    if (live && lane == 0) out[seg] = s;
+  }
+}
+
+template <int L, class Idx>
+__global__ __launch_bounds__(WG) void k_jacobi(i64 nrows, const i64 *__restrict__ rowptr, const Idx *__restrict__ col, const double *__restrict__ values,
+                                               const double *__restrict__ x, const double *__restrict__ w, const double *__restrict__ b,
+                                               const unsigned char *__restrict__ mask, double *__restrict__ y) {
+  constexpr int G = WG / L;
+  const int lane = threadIdx.x & (L - 1);
+  for (i64 base = (i64)blockIdx.x * G; base < nrows; base += (i64)gridDim.x * G) {
+    const i64 row = base + threadIdx.x / L;
+    const bool live = row < nrows;
+    const bool on = live && (!mask || mask[row]);
+    double s = 0;
+    if (on) {
+      const i64 k1 = rowptr[row + 1];
+#pragma unroll 2
+      for (i64 k = rowptr[row] + lane; k < k1; k += L) s += values[k] * x[col[k]];
+    }
+#pragma unroll
+    for (int o = L >> 1; o; o >>= 1) s += __shfl_xor(s, o, L);
+    if (live && lane == 0) y[row] = on ? x[row] + w[row] * (b[row] - s) : 0.;
+  }
+}
+
+__global__ __launch_bounds__(WG) void k_scale(i64 n, const double *__restrict__ w, const double *__restrict__ b, double *__restrict__ y) {
+  for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < n; i += (i64)gridDim.x * WG) y[i] = w[i] * b[i];
+}
+
+// z[idx[i]] = sum_j Ainv[i][j] b[idx[j]], i < m (idx == NULL: the identity); other rows of z are not touched (the caller has zeroed them).  One workgroup: a
+// wave per row, its lanes stride over the columns and are folded in a fixed order.
+__global__ __launch_bounds__(DENSE_WG) void k_dense(int m, const double *__restrict__ Ainv, const double *__restrict__ b, const int32_t *__restrict__ idx,
+                                                    double *__restrict__ z) {
+  __shared__ double bs[1024];
+  for (int j = threadIdx.x; j < m; j += DENSE_WG) bs[j] = b[idx ? idx[j] : j];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int i = wave; i < m; i += DENSE_WG / 64) {
+    const double *row = Ainv + (i64)i * m;
+    double s = 0;
+    for (int j = lane; j < m; j += 64) s += row[j] * bs[j];
+#pragma unroll
+    for (int o = 32; o; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (lane == 0) z[idx ? idx[i] : i] = s;
+  }
+}
+
+// p = z, partials of r . z and r . r
+__global__ __launch_bounds__(WG) void k_pcg_init(i64 n, double *work, const double *__restrict__ r, const double *__restrict__ z, double *__restrict__ p) {
+  __shared__ double lds[4];
+  double rz = 0, rr = 0;
+  for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < n; i += (i64)gridDim.x * WG) {
+    const double ri = r[i], zi = z[i];
+    p[i] = zi;
+    rz += ri * zi;
+    rr += ri * ri;
+  }
+  rz = block_sum(rz, lds);
+  rr = block_sum(rr, lds);
+  if (threadIdx.x == 0) {
+    work[P_RZP + blockIdx.x] = rz;
+    work[P_RRP + blockIdx.x] = rr;
+  }
+}
+
+__global__ __launch_bounds__(WG) void k_pcg_init_scalars(int nparts, double *work) {
+  __shared__ double lds[4];
+  const double rz = partial_sum(work + P_RZP, nparts, lds);
+  const double rr = partial_sum(work + P_RRP, nparts, lds);
+  if (threadIdx.x == 0) {
+    work[W_RR] = rr;
+    work[P_RZ_B] = rz;
+    work[P_RZ_A] = rz;
+    work[P_FLAG_A] = 0.;
+    work[W_FLAG_B] = 0.;
+    work[W_STOP] = 0.;
+  }
+}
+
+// alpha = r.z / p.q;  x += alpha p;  r -= alpha q;  partials of r . r.  reads RR, RZ_B, FLAG_A, STOP, the p.q partials; writes RZ_A, FLAG_B, the r.r partials
+// (not when done or stalled: r has not moved, they stand)
+__global__ __launch_bounds__(WG) void k_pcg_update(i64 n, int npq, double *work, double *__restrict__ x, double *__restrict__ r, const double *__restrict__ p,
+                                                   const double *__restrict__ q) {
+  __shared__ double lds[4];
+  const double pq = partial_sum(work + P_PQ, npq, lds);
+  const double rz = work[P_RZ_B], rr = work[W_RR];
+  bool bad = work[P_FLAG_A] != 0.;
+  const bool done = rr <= work[W_STOP];  // (within the bound: nothing left to do, and p . q = 0 is no breakdown)
+  if (!done && !bad) bad = !(rz > 0. && rz <= 1.7976931348623157e308 && pq > 0. && pq <= 1.7976931348623157e308);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    work[P_RZ_A] = rz;
+    work[W_FLAG_B] = bad ? 1. : 0.;
+  }
+  if (done || bad) return;
+  const double alpha = rz / pq;
+  double srr = 0;
+  for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < n; i += (i64)gridDim.x * WG) {
+    x[i] += alpha * p[i];
+    const double ri = r[i] - alpha * q[i];
+    r[i] = ri;
+    srr += ri * ri;
+  }
+  srr = block_sum(srr, lds);
+  if (threadIdx.x == 0) work[P_RRP + blockIdx.x] = srr;
+}
+
+// partials of r . z, z = M r of the cycle just run
+__global__ __launch_bounds__(WG) void k_pcg_dot(i64 n, double *work, const double *__restrict__ r, const double *__restrict__ z) {
+  __shared__ double lds[4];
+  double rz = 0;
+  for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < n; i += (i64)gridDim.x * WG) rz += r[i] * z[i];
+  rz = block_sum(rz, lds);
+  if (threadIdx.x == 0) work[P_RZP + blockIdx.x] = rz;
+}
+
+// beta = r.z (new) / r.z (old);  p = z + beta p (not once r . r is within the bound, nor after a breakdown).  reads RZ_A, FLAG_B, STOP, the partials; writes RR,
+// RZ_B, FLAG_A
+__global__ __launch_bounds__(WG) void k_pcg_direction(i64 n, int nparts, double *work, const double *__restrict__ z, double *__restrict__ p) {
+  __shared__ double lds[4];
+  const double rz = partial_sum(work + P_RZP, nparts, lds);
+  const double rr = partial_sum(work + P_RRP, nparts, lds);
+  const double rz_old = work[P_RZ_A];
+  const bool bad = work[W_FLAG_B] != 0.;
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    work[W_RR] = rr;
+    work[P_RZ_B] = bad ? rz_old : rz;
+    work[P_FLAG_A] = bad ? 1. : 0.;
+  }
+  if (bad || rr <= work[W_STOP]) return;
+  const double beta = rz_old != 0. ? rz / rz_old : 0.;
+  for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < n; i += (i64)gridDim.x * WG) p[i] = z[i] + beta * p[i];
+}
+
+template <class Idx>
+void launch_jacobi(int L, const nh_csr &A, const Idx *col, const double *x, const double *w, const double *b, const unsigned char *mask, double *y, hipStream_t s) {
+#define NH_JACOBI(LL)                                                                                                                                                    \
+  case LL:                                                                                                                                                               \
+    hipLaunchKernelGGL((k_jacobi<LL, Idx>), dim3(spmv_grid(A.nrows, LL)), dim3(WG), 0, s, (i64)A.nrows, (const i64 *)A.rowptr_dev, col, A.values_dev, x, w, b, mask, y); \
+    break;
+  switch (L) {
+    NH_JACOBI(1)
+    NH_JACOBI(2)
+    NH_JACOBI(4)
+    NH_JACOBI(8)
+    NH_JACOBI(16)
+    NH_JACOBI(32)
+    default:
+    NH_JACOBI(64)
+  }
+#undef NH_JACOBI
+}
+
+// y = mask(x + w (b - A x)); the caller has checked the view
+int jacobi(const nh_csr &A, const double *x, const double *w, const double *b, const unsigned char *mask, double *y, hipStream_t s) {
+  if (!A.nrows) return NH_OK;
+  const int L = A.lanes ? A.lanes : nh_csr_lanes(A.nrows, A.nnz);
+  if (A.col32_dev)
+    launch_jacobi(L, A, A.col32_dev, x, w, b, mask, y, s);
+  else
+    launch_jacobi(L, A, (const i64 *)A.colidx_dev, x, w, b, mask, y, s);
+  NH_LAUNCH_CHECK();
+  return NH_OK;
+}
+
+int scale(i64 n, const double *w, const double *b, double *y, hipStream_t s) {
+  if (!n) return NH_OK;
+  hipLaunchKernelGGL(k_scale, dim3(vec_grid(n)), dim3(WG), 0, s, n, w, b, y);
+  NH_LAUNCH_CHECK();
+  return NH_OK;
+}
+
+// x = M b on level l.  The sweeps alternate between the level's two vectors: there are 2 sweeps - 1 that swap, so the cycle starts in t and ends in x.
+int amg_cycle(const nh_amg *h, size_t l, const double *b, double *x, hipStream_t s) {
+  const nh_amg_level &lv = h->levels[l];
+  const i64 n = lv.A.nrows;
+  if (!n) return NH_OK;
+  if (lv.kind == NH_AMG_DENSE) {
+    if (lv.ndense < n) NH_CHECK_HIP(hipMemsetAsync(x, 0, sizeof(double) * (size_t)n, s));  // (a masked level 0: the rows the dense block does not reach are 0)
+    if (!lv.ndense) return NH_OK;
+    hipLaunchKernelGGL(k_dense, dim3(1), dim3(DENSE_WG), 0, s, (int)lv.ndense, lv.Ainv_dev, b, lv.idx_dev, x);
+    NH_LAUNCH_CHECK();
+    return NH_OK;
+  }
+  if (lv.kind == NH_AMG_DIAGONAL) return scale(n, lv.w_dev, b, x, s);
+  const nh_amg_level &next = h->levels[l + 1];
+  double *cur = lv.t_dev, *other = x;
+  if (int rc = scale(n, lv.w_dev, b, cur, s)) return rc;
+  for (int k = 1; k < lv.sweeps; ++k) {
+    if (int rc = jacobi(lv.A, cur, lv.w_dev, b, lv.rowmask_dev, other, s)) return rc;
+    std::swap(cur, other);
+  }
+  if (int rc = nh_csr_spmv(&lv.A, -1., cur, 1., b, lv.rowmask_dev, lv.r_dev, s)) return rc;
+  if (int rc = nh_csr_spmv(&lv.R, 1., lv.r_dev, 0., nullptr, nullptr, next.b_dev, s)) return rc;
+  if (int rc = amg_cycle(h, l + 1, next.b_dev, next.x_dev, s)) return rc;
+  if (int rc = nh_csr_spmv(&lv.P, 1., next.x_dev, 1., cur, nullptr, cur, s)) return rc;
+  for (int k = 0; k < lv.sweeps; ++k) {
+    if (int rc = jacobi(lv.A, cur, lv.w_dev, b, lv.rowmask_dev, other, s)) return rc;
+    std::swap(cur, other);
+  }
+  return NH_OK;  // (cur == x)
+}
+
+}  // namespace
+
+extern "C" {
+
+int nh_segment_dot(int64_t nseg, const int64_t *ptr_dev, const int32_t *ia_dev, const int32_t *ib_dev, const double *a_dev, const double *b_dev, int64_t nprod,
+                   double *out_dev, void *stream) {
+  NH_REQUIRE(nseg >= 0 && nprod >= 0, "nh_segment_dot: negative size");
+  NH_REQUIRE(!nseg || (ptr_dev && out_dev), "nh_segment_dot: NULL segment pointers or result");
+  NH_REQUIRE(!nprod || (ia_dev && a_dev), "nh_segment_dot: NULL first factor");
+  NH_REQUIRE(!b_dev || !nprod || ib_dev, "nh_segment_dot: a second factor without its indices");
+  if (!nseg) return NH_OK;
+  hipStream_t s = nh_stream(stream);
+  const i64 *ptr = (const i64 *)ptr_dev;
+#define NH_SEGDOT(LL)                                                                                                                          \
+  case LL:                                                                                                                                     \
+    hipLaunchKernelGGL(k_segment_dot<LL>, dim3(spmv_grid(nseg, LL)), dim3(WG), 0, s, (i64)nseg, ptr, ia_dev, ib_dev, a_dev, b_dev, out_dev); \
+    break;
+  switch (nh_csr_lanes(nseg, nprod)) {
+    NH_SEGDOT(1)
+    NH_SEGDOT(2)
+    NH_SEGDOT(4)
+    NH_SEGDOT(8)
+    NH_SEGDOT(16)
+    default:
+    NH_SEGDOT(32)
+  }
+#undef NH_SEGDOT
+  NH_LAUNCH_CHECK();
+  return NH_OK;
+}
+
+int nh_csr_jacobi(const nh_csr *A, const double *x_dev, const double *w_dev, const double *b_dev, const unsigned char *rowmask_dev, double *y_dev, void *stream) {
+  if (int rc = check_csr("nh_csr_jacobi", A)) return rc;
+  NH_REQUIRE(A->nrows == A->ncols, "nh_csr_jacobi: the matrix must be square (got %lld x %lld)", (long long)A->nrows, (long long)A->ncols);
+  NH_REQUIRE(!A->nrows || (x_dev && w_dev && b_dev && y_dev), "nh_csr_jacobi: NULL vector");
+  NH_REQUIRE(!A->nrows || x_dev != y_dev, "nh_csr_jacobi: the result must not be the argument");
+  return jacobi(*A, x_dev, w_dev, b_dev, rowmask_dev, y_dev, nh_stream(stream));
+}
+
+int nh_amg_create(const nh_amg_level *levels, int nlevels, nh_amg **out) {
+  NH_REQUIRE(levels && nlevels >= 1 && out, "nh_amg_create: no levels, or nowhere to put the handle");
+  for (int l = 0; l < nlevels; ++l) {
+    const nh_amg_level &lv = levels[l];
+    const bool last = l == nlevels - 1;
+    const i64 n = lv.A.nrows;
+    if (int rc = check_csr("nh_amg_create (a level matrix)", &lv.A)) return rc;
+    NH_REQUIRE(n == lv.A.ncols, "nh_amg_create: level %d is not square", l);
+    NH_REQUIRE(lv.kind == NH_AMG_COARSEN || lv.kind == NH_AMG_DENSE || lv.kind == NH_AMG_DIAGONAL, "nh_amg_create: level %d has an unknown kind %d", l, lv.kind);
+    NH_REQUIRE((lv.kind == NH_AMG_COARSEN) == !last, "nh_amg_create: every level but the last is coarsened, the last is not (level %d)", l);
+    NH_REQUIRE(l == 0 || !n || (lv.b_dev && lv.x_dev), "nh_amg_create: level %d lacks its right-hand side or solution vector", l);
+    if (lv.kind == NH_AMG_DENSE) {
+      NH_REQUIRE(lv.ndense >= 0 && lv.ndense <= 1024 && lv.ndense <= n, "nh_amg_create: the dense level has %lld unknowns (at most 1024, and no more than rows)", (long long)lv.ndense);
+      NH_REQUIRE(!lv.ndense || lv.Ainv_dev, "nh_amg_create: NULL dense inverse");
+      NH_REQUIRE(lv.ndense == n || lv.idx_dev || !lv.ndense, "nh_amg_create: a dense level smaller than its vectors needs its index list");
+    } else {
+      NH_REQUIRE(!n || lv.w_dev, "nh_amg_create: level %d lacks its weights", l);
+    }
+    if (lv.kind == NH_AMG_COARSEN) {
+      const i64 nc = levels[l + 1].A.nrows;
+      NH_REQUIRE(lv.sweeps >= 1, "nh_amg_create: level %d: sweeps must be at least 1 (got %d)", l, lv.sweeps);
+      NH_REQUIRE(!n || (lv.t_dev && lv.r_dev), "nh_amg_create: level %d lacks its work vectors", l);
+      if (int rc = check_csr("nh_amg_create (a prolongator)", &lv.P)) return rc;
+      if (int rc = check_csr("nh_amg_create (a restriction)", &lv.R)) return rc;
+      NH_REQUIRE(lv.P.nrows == n && lv.P.ncols == nc && lv.R.nrows == nc && lv.R.ncols == n, "nh_amg_create: level %d: P is %lld x %lld and R %lld x %lld between %lld and %lld dofs", l,
+                 (long long)lv.P.nrows, (long long)lv.P.ncols, (long long)lv.R.nrows, (long long)lv.R.ncols, (long long)n, (long long)nc);
+    }
+  }
+  nh_amg *h = new (std::nothrow) nh_amg;
+  NH_REQUIRE(h, "nh_amg_create: out of memory");
+  h->levels.assign(levels, levels + nlevels);
+  *out = h;
+  return NH_OK;
+}
+
+int nh_amg_free(nh_amg *amg) {
+  delete amg;
+  return NH_OK;
+}
+
+int nh_amg_apply(const nh_amg *amg, const double *r_dev, double *z_dev, void *stream) {
+  NH_REQUIRE(amg, "nh_amg_apply: NULL hierarchy");
+  NH_REQUIRE(!amg->levels[0].A.nrows || (r_dev && z_dev && r_dev != z_dev), "nh_amg_apply: NULL vector, or the result is the argument");
+  return amg_cycle(amg, 0, r_dev, z_dev, nh_stream(stream));
+}
+
+int64_t nh_pcg_work_doubles(void) { return P_END; }
+
+int nh_pcg_init(int64_t n, const nh_amg *amg, const double *r_dev, double *z_dev, double *p_dev, double *work_dev, void *stream) {
+  NH_REQUIRE(n >= 0, "nh_pcg_init: negative size");
+  NH_REQUIRE(amg && amg->levels[0].A.nrows == n, "nh_pcg_init: NULL hierarchy, or one of another size");
+  NH_REQUIRE(work_dev && (!n || (r_dev && z_dev && p_dev && r_dev != z_dev)), "nh_pcg_init: NULL vector");
+  hipStream_t s = nh_stream(stream);
+  const unsigned grid = vec_grid(n);
+  if (n) {
+    if (int rc = amg_cycle(amg, 0, r_dev, z_dev, s)) return rc;
+    hipLaunchKernelGGL(k_pcg_init, dim3(grid), dim3(WG), 0, s, (i64)n, work_dev, r_dev, (const double *)z_dev, p_dev);
+    NH_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_pcg_init_scalars, dim3(1), dim3(WG), 0, s, (int)grid, work_dev);
+  NH_LAUNCH_CHECK();
+  return NH_OK;
+}
+
+int nh_pcg_iterate(const nh_csr *A, const unsigned char *rowmask_dev, const nh_amg *amg, double *x_dev, double *r_dev, double *z_dev, double *p_dev, double *q_dev,
+                   double *work_dev, int niter, void *stream) {
+  NH_REQUIRE(A, "nh_pcg_iterate: NULL matrix");
+  NH_REQUIRE(A->nrows == A->ncols, "nh_pcg_iterate: the matrix must be square (got %lld x %lld)", (long long)A->nrows, (long long)A->ncols);
+  NH_REQUIRE(niter >= 0, "nh_pcg_iterate: negative iteration count");
+  NH_REQUIRE(amg && amg->levels[0].A.nrows == A->nrows, "nh_pcg_iterate: NULL hierarchy, or one of another size");
+  NH_REQUIRE(work_dev && (!A->nrows || (x_dev && r_dev && z_dev && p_dev && q_dev)), "nh_pcg_iterate: NULL vector");
+  hipStream_t s = nh_stream(stream);
+  const i64 n = A->nrows;
+  const unsigned grid = vec_grid(n);
+  for (int it = 0; it < niter; ++it) {
+    int npq = 0;
+    if (int rc = nh_csr_spmv_pq(A, p_dev, rowmask_dev, q_dev, work_dev + P_PQ, SPMV_MAX_WGS, &npq, s)) return rc;
+    if (!n) return NH_OK;
+    hipLaunchKernelGGL(k_pcg_update, dim3(grid), dim3(WG), 0, s, n, npq, work_dev, x_dev, r_dev, (const double *)p_dev, (const double *)q_dev);
+    NH_LAUNCH_CHECK();
+    if (int rc = amg_cycle(amg, 0, r_dev, z_dev, s)) return rc;
+    hipLaunchKernelGGL(k_pcg_dot, dim3(grid), dim3(WG), 0, s, n, work_dev, (const double *)r_dev, (const double *)z_dev);
+    NH_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_pcg_direction, dim3(grid), dim3(WG), 0, s, n, (int)grid, work_dev, (const double *)z_dev, p_dev);
+    NH_LAUNCH_CHECK();
+  }
+  return NH_OK;
+}
+
+}  // extern "C"

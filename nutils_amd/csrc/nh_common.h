@@ -36,6 +36,10 @@ static inline hipStream_t nh_stream(void *s) { return reinterpret_cast<hipStream
 int nh_scan_exclusive(const int32_t *in_dev, i64 *out_dev, i64 n, hipStream_t stream);
 int nh_scan_exclusive64(const i64 *in_dev, i64 *out_dev, i64 n, hipStream_t stream);
 
+// nh_csr.hip, for the solvers of other files: q = mask(A p) and the per-workgroup partials of p . q (the product of a CG step); *npartials: how many were written
+int nh_csr_spmv_pq(const nh_csr *A, const double *p_dev, const unsigned char *rowmask_dev, double *q_dev, double *partial_dev, int max_partials, int *npartials,
+                   hipStream_t stream);
+
 // geometry / basis structs are passed by value to kernels
 struct GeomK {
   int kind, ngb;

@@ -28,29 +28,10 @@
 
 namespace {
 
-constexpr int WG = 256;
-constexpr int SPMV_MAX_WGS = 2048;  // 8 waves per SIMD on 256 CUs; also the number of p . Ap partials every workgroup of k_cg_update sums
-constexpr int VEC_MAX_WGS = 1024;
+#include "nh_krylov.inc"  // WG, the grid caps, block_sum, partial_sum, check_csr, spmv_grid, vec_grid, and the cells W_RR, W_FLAG_B, W_STOP: shared with nh_amg.hip
 
-// cells of the CG work array (doubles); the first three are the caller's to read (RR, FLAG_B) and to write (STOP: nh_cg_init clears it, the kernels only read it)
-enum { W_RR = 0, W_FLAG_B = 1, W_STOP = 2, W_FLAG_A = 3, W_RZ_A = 4, W_RZ_B = 5, W_PQ = 8, W_RZP = W_PQ + SPMV_MAX_WGS, W_RRP = W_RZP + VEC_MAX_WGS, W_END = W_RRP + VEC_MAX_WGS };
-
-// sum over the workgroup in a fixed order; every thread returns the total
-__device__ __forceinline__ double block_sum(double s, double *lds) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) s += __shfl_xor(s, o, 64);
-  __syncthreads();  // (lds may still be read from a previous call)
-  if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
-  __syncthreads();
-  return ((lds[0] + lds[1]) + lds[2]) + lds[3];
-}
-
-// sum of n partials, the same order in every workgroup
-__device__ __forceinline__ double partial_sum(const double *part, int n, double *lds) {
-  double s = 0;
-  for (int j = threadIdx.x; j < n; j += WG) s += part[j];
-  return block_sum(s, lds);
-}
+// the other cells of the CG work array (doubles)
+enum { W_FLAG_A = 3, W_RZ_A = 4, W_RZ_B = 5, W_PQ = 8, W_RZP = W_PQ + SPMV_MAX_WGS, W_RRP = W_RZP + VEC_MAX_WGS, W_END = W_RRP + VEC_MAX_WGS };
 
 template <int L, class Idx, int DOT>
 __global__ __launch_bounds__(WG) void k_csr_spmv(i64 nrows, const i64 *__restrict__ rowptr, const Idx *__restrict__ col, const double *__restrict__ values,
@@ -724,21 +705,6 @@ __global__ __launch_bounds__(WG) void k_gmres_xupdate(i64 n, int m, const double
 }
 #undef NH_GS_ROWS
 
-bool lanes_ok(int lanes) { return lanes >= 0 && lanes <= 64 && (lanes & (lanes - 1)) == 0; }
-
-int check_csr(const char *who, const nh_csr *A) {
-  NH_REQUIRE(A, "%s: NULL matrix", who);
-  NH_REQUIRE(A->nrows >= 0 && A->ncols >= 0 && A->nnz >= 0, "%s: negative size (%lld x %lld, %lld entries)", who, (long long)A->nrows, (long long)A->ncols, (long long)A->nnz);
-  NH_REQUIRE(lanes_ok(A->lanes), "%s: lanes per row must be 0 or a power of two <= 64 (got %d)", who, A->lanes);
-  NH_REQUIRE(!A->nrows || A->rowptr_dev, "%s: NULL row pointers", who);
-  NH_REQUIRE(!A->nnz || (A->values_dev && (A->colidx_dev || A->col32_dev)), "%s: NULL values or column indices", who);
-  NH_REQUIRE(!A->col32_dev || A->ncols <= INT32_MAX, "%s: int32 column indices cannot address %lld columns", who, (long long)A->ncols);
-  return NH_OK;
-}
-
-unsigned spmv_grid(i64 nrows, int L) { return (unsigned)std::min<i64>((nrows + WG / L - 1) / (WG / L), SPMV_MAX_WGS); }
-unsigned vec_grid(i64 n) { return (unsigned)std::min<i64>((n + WG - 1) / WG, VEC_MAX_WGS); }
-
 // what a product leaves besides y: nothing (partial == NULL), the partials of x . y (w == NULL), or those of w . y and y . y; with a skip cell and no
 // partials the plain product, not done when the cell is set
 struct Epilogue {
@@ -849,6 +815,21 @@ int gmres_steps(const nh_csr *B, const unsigned char *rowmask, const double *din
 }
 
 }  // namespace
+
+int nh_csr_spmv_pq(const nh_csr *A, const double *p_dev, const unsigned char *rowmask_dev, double *q_dev, double *partial_dev, int max_partials, int *npartials,
+                   hipStream_t s) {
+  if (int rc = check_csr("nh_csr_spmv_pq", A)) return rc;
+  NH_REQUIRE(partial_dev && npartials && (!A->nrows || (p_dev && q_dev)), "nh_csr_spmv_pq: NULL vector");
+  NH_REQUIRE(max_partials >= SPMV_MAX_WGS, "nh_csr_spmv_pq: room for %d partials, a product may leave %d", max_partials, SPMV_MAX_WGS);
+  *npartials = 0;
+  if (!A->nrows) return NH_OK;
+  nh_csr B = *A;
+  B.lanes = A->lanes ? A->lanes : nh_csr_lanes(A->nrows, A->nnz);
+  *npartials = (int)spmv_grid(A->nrows, B.lanes);
+  Epilogue pq;
+  pq.partial = partial_dev;
+  return spmv(&B, 1., p_dev, 0., nullptr, rowmask_dev, q_dev, pq, s);
+}
 
 extern "C" {
 

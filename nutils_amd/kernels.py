@@ -938,3 +938,75 @@ def gmres_iterate(values, rowptr, colidx, ncols, *, rowmask, dinv, V, z, w, work
 def gmres_update(dinv, V, x, work, *, restart):
     '''x += dinv V y for the columns the cycle has taken (nh_gmres_update)'''
     _lib.call('nh_gmres_update', x.numel(), int(restart), device.ptr(dinv), device.ptr(V), device.ptr(x), device.ptr(work), device.stream())
+
+
+# ---- smoothed-aggregation AMG and the CG it preconditions (nh_amg.hip) --------------------------------
+
+def segment_dot(plan, a, b=None, out=None):
+    '''out[s] = sum of a[ia[k]] * b[ib[k]] over the products of segment s of an expand-sort-compress plan (`amg.Plan`; nh_segment_dot); without `b` the
+    segment sum of a[ia[k]]'''
+    if out is None:
+        out = device.empty(plan.nseg, 'float64')
+    _lib.call('nh_segment_dot', plan.nseg, device.ptr(plan.ptr), device.ptr(plan.ia), device.ptr(plan.ib if b is not None else None), device.ptr(a), device.ptr(b),
+              plan.nprod, device.ptr(out), device.stream())
+    return out
+
+
+def csr_jacobi(values, rowptr, colidx, ncols, x, w, b, *, y=None, rowmask=None, col32=None, lanes=0):
+    '''y = x + w (b - A x) on the rows the mask keeps, 0 elsewhere, in one launch (nh_csr_jacobi)'''
+    if y is None:
+        y = device.empty(rowptr.numel() - 1, 'float64')
+    _lib.call('nh_csr_jacobi', ctypes.byref(_csr(values, rowptr, colidx, ncols, col32, lanes)), device.ptr(x), device.ptr(w), device.ptr(b), device.ptr(rowmask),
+              device.ptr(y), device.stream())
+    return y
+
+
+class Amg:
+    '''The handle of a hierarchy (nh_amg_create / nh_amg_free).  `levels`: one dict per level with A, and P, R for a coarsened level, as (values, rowptr,
+    colidx, ncols, col32, lanes); rowmask, w, b, x, t, r, Ainv, idx: device tensors or None; kind: 'coarsen', 'dense' or 'diagonal'; sweeps; ndense.  The
+    handle holds views: this object keeps the tensors alive.'''
+
+    def __init__(self, levels):
+        self._keep = levels
+        self.n = levels[0]['A'][1].numel() - 1
+        array = (_lib.AmgLevel * len(levels))()
+        for lv, d in zip(array, levels):
+            lv.A = _csr(*d['A'])
+            for name in ('P', 'R'):
+                if d.get(name) is not None:
+                    setattr(lv, name, _csr(*d[name]))
+            for name in ('rowmask', 'w', 'b', 'x', 't', 'r', 'Ainv', 'idx'):
+                setattr(lv, name + '_dev', device.ptr(d.get(name)))
+            lv.kind, lv.sweeps, lv.ndense = _lib.AMG_KINDS[d['kind']], int(d.get('sweeps', 1)), int(d.get('ndense', 0))
+        self._handle = ctypes.c_void_p()
+        _lib.call('nh_amg_create', array, len(levels), ctypes.byref(self._handle))
+
+    def __del__(self):
+        handle, self._handle = getattr(self, '_handle', None), None
+        if handle:
+            _lib.load().nh_amg_free(handle)
+
+    def apply(self, r, z=None):
+        '''z = M r: one V-cycle, enqueued (nh_amg_apply)'''
+        if z is None:
+            z = device.empty(self.n, 'float64')
+        _lib.call('nh_amg_apply', self._handle, device.ptr(r), device.ptr(z), device.stream())
+        return z
+
+
+def pcg_work():
+    '''the work array of a CG solve with a cycle as its preconditioner (nh_pcg_work_doubles): [0] = r . r of the recurrence, [1] = breakdown flag, [2] = the
+    bound of `cg_stop`'''
+    return device.empty(_lib.load().nh_pcg_work_doubles(), 'float64')
+
+
+def pcg_init(amg, r, z, p, work):
+    '''z = M r, p = z, first r . z and r . r, flag and bound cleared (nh_pcg_init)'''
+    _lib.call('nh_pcg_init', r.numel(), amg._handle, device.ptr(r), device.ptr(z), device.ptr(p), device.ptr(work), device.stream())
+
+
+def pcg_iterate(values, rowptr, colidx, ncols, *, rowmask, amg, x, r, z, p, q, work, niter, col32=None, lanes=0):
+    '''enqueue `niter` CG iterations preconditioned by the cycle of `amg` (nh_pcg_iterate): four launches and a cycle each, nothing read back; they stop
+    moving once r . r is within the bound of `cg_stop`'''
+    _lib.call('nh_pcg_iterate', ctypes.byref(_csr(values, rowptr, colidx, ncols, col32, lanes)), device.ptr(rowmask), amg._handle, device.ptr(x), device.ptr(r),
+              device.ptr(z), device.ptr(p), device.ptr(q), device.ptr(work), int(niter), device.stream())

@@ -169,7 +169,7 @@ class HipMatrix:
     (12 instead of 16 bytes per entry; matrices with more than 2^31 - 1 columns keep the int64 indices).
 
     On the device: products (nh_csr_spmv), the diagonal, `rowsupp` / `colsupp` (nh_csr_support), scalar multiples, sums of matrices that share their index tensors, `solve(solver='cg')`, a
-    Jacobi-preconditioned conjugate-gradient iteration for SYMMETRIC POSITIVE DEFINITE systems, and for ANY square system (nonsymmetric, indefinite)
+    conjugate-gradient iteration for SYMMETRIC POSITIVE DEFINITE systems preconditioned by Jacobi or by a smoothed-aggregation multigrid cycle (`precon='amg'`, amg.py), and for ANY square system (nonsymmetric, indefinite)
     `solve(solver='bicgstab')`, a Jacobi-preconditioned BiCGStab iteration, and `solve(solver='fgmres')`, Jacobi-preconditioned restarted GMRES, whose residual
     norm never rises within a cycle; all with ONE right-hand side.  `iterations` is the iteration count of the last device solve.  Through scipy and PCIe (export, host operation, re-upload): `submatrix`, `T`, sums of matrices with different patterns, every other solver.'''
 
@@ -192,6 +192,7 @@ class HipMatrix:
         self.cg_iterations = None
         self.iterations = None
         self._col32 = None
+        self._amg = None  # (free mask, coarse, levels) of the last 'amg' setup: the symbolic phase, reused while pattern and mask stay
 
     @property
     def size(self):
@@ -215,10 +216,11 @@ class HipMatrix:
         return self._col32
 
     def _with_values(self, values):
-        '''a matrix on the same index tensors (and their int32 copy)'''
+        '''a matrix on the same index tensors (and their int32 copy, and the symbolic phase of an 'amg' preconditioner with the mask it was made for)'''
         _, rowptr, colidx = self.triplet()
         new = HipMatrix(values, rowptr, colidx, self._ncols)
         new._col32 = self._col32
+        new._amg = self._amg
         return new
 
     def spmv(self, x, *, alpha=1., beta=0., b=None, rowmask=None, y=None, lanes=None):
@@ -335,7 +337,7 @@ class HipMatrix:
 
     # -- solve
 
-    def solve(self, rhs=None, *, lhs0=None, constrain=None, solver='cg', atol=0., rtol=0., precon='diag', maxiter=None, check=16, restart=30, **solverargs):
+    def solve(self, rhs=None, *, lhs0=None, constrain=None, solver='cg', atol=0., rtol=0., precon='diag', maxiter=None, check=16, restart=30, preconargs=None, **solverargs):
         '''Solve A x = rhs with constraints in the reference's convention (`constraints`; Matrix.solve, matrix/_base.py:100-176).
 
         solver='cg': conjugate gradients on the device for a SYMMETRIC POSITIVE DEFINITE matrix and ONE right-hand side.  No submatrix is formed: the free
@@ -343,7 +345,11 @@ class HipMatrix:
         product ignores constrained columns by itself -- the iteration is that of the reference's submatrix(free, free).  It stops when the recurrence has
         |r| <= max(atol, rtol |r0|), and the iterations enqueued after that one do nothing; the true residual is then recomputed, and the iteration restarts from
         it should rounding have left it above the bound.
-        An iterative solve has no "machine precision" mode: atol = rtol = 0 is an error, not a request for it.  `precon`: 'diag' (Jacobi) or None.
+        An iterative solve has no "machine precision" mode: atol = rtol = 0 is an error, not a request for it.  `precon`: 'diag' (Jacobi), None, or -- for this
+        solver alone -- 'amg': a smoothed-aggregation multigrid V-cycle (the `amg` module has the algorithm), `preconargs=dict(coarse=256, sweeps=1)`: the
+        coarsest level has at most `coarse` (1 .. 1024) dofs and is solved densely, its matrix the only thing that visits the host; `sweeps` Jacobi sweeps before
+        and after each coarse correction.  Its symbolic phase runs once per pattern, mask and `coarse` and is handed on by `_with_values`.  The near-nullspace
+        is the constant: a vector problem such as elasticity gets a valid preconditioner, not an optimal one.
         `maxiter` defaults to the number of free dofs; `check`: iterations enqueued between two looks at the device's residual norm and breakdown flag (one
         16-byte copy).  Raises ToleranceNotReached(best) when the bound is not met, MatrixError when the matrix turns out not to be positive definite.
 
@@ -383,14 +389,22 @@ class HipMatrix:
             return x
         if not (atol > 0 or rtol > 0):
             raise MatrixError(f"solver {solver!r} needs a tolerance: pass atol or rtol (an iterative solve has no machine-precision mode)")
-        if precon not in ('diag', None):
-            raise MatrixError(f'invalid preconditioner {precon!r} for HipMatrix: \'diag\' or None')
+        if precon == 'amg' and solver == 'cg':
+            from . import amg
+            preconargs = amg.check_args(preconargs)
+        elif precon not in ('diag', None):
+            raise MatrixError(f"invalid preconditioner {precon!r} for HipMatrix solver {solver!r}: 'diag' or None" + (", or 'amg'" if solver == 'cg' else ''))
+        elif preconargs is not None:
+            raise MatrixError(f"preconargs are the arguments of precon='amg'; the preconditioner {precon!r} takes none")
         if solver == 'fgmres' and not (isinstance(restart, (int, numpy.integer)) and not isinstance(restart, bool) and restart >= 1):
             raise MatrixError(f'fgmres: restart must be an integer of at least 1, got {restart!r}')
         free, lhs = constraints(ncols, _host(constrain), _host(lhs0))
-        krylov = self._cg if solver == 'cg' else self._bicgstab if solver == 'bicgstab' else self._fgmres
         args = (rhs, free, lhs, atol, rtol, precon, int(free.sum()) if maxiter is None else int(maxiter), max(1, int(check)), on_device)
-        return krylov(*args, int(restart)) if solver == 'fgmres' else krylov(*args)
+        if solver == 'cg':
+            return self._cg(*args, preconargs)
+        if solver == 'bicgstab':
+            return self._bicgstab(*args)
+        return self._fgmres(*args, int(restart))
 
     def solve_leniently(self, *args, **kwargs):
         '''`solve` that returns the vector reached instead of raising ToleranceNotReached'''
@@ -417,19 +431,37 @@ class HipMatrix:
             dinv = (1. / diag).masked_fill(~keep | (diag == 0), 0.)  # (constrained rows: any finite number, their residual is zero)
         return mask, x, b, dinv
 
-    def _cg(self, rhs, free, lhs, atol, rtol, precon, maxiter, check, on_device):
+    def _amg_hierarchy(self, free, mask, coarse, sweeps):
+        '''the hierarchy of an 'amg' preconditioner (amg.Hierarchy): the symbolic phase is taken from the cache if it was made for this mask and this `coarse`,
+        the numeric phase runs on the values of this matrix'''
+        from . import amg
+        _, rowptr, colidx = self.triplet()
+        if self._amg is None or self._amg[1] != coarse or not numpy.array_equal(self._amg[0], free):
+            self._amg = free.copy(), coarse, amg.symbolic(rowptr, colidx, None if mask is None else mask != 0, coarse)
+        return amg.Hierarchy(self._amg[2], self.triplet()[0], sweeps)
+
+    def _cg(self, rhs, free, lhs, atol, rtol, precon, maxiter, check, on_device, preconargs=None):
         from . import device, kernels
         n = self.shape[0]
         values, rowptr, colidx = self.triplet()
-        mask, x, b, dinv = self._krylov_setup(rhs, free, lhs, precon, on_device)
+        mask, x, b, dinv = self._krylov_setup(rhs, free, lhs, None if precon == 'amg' else precon, on_device)
         r, p, q = (device.empty(n, 'float64') for _ in range(3))
-        work = kernels.cg_work()
+        csr = dict(rowmask=mask, x=x, r=r, p=p, q=q, col32=self._columns(), lanes=self.lanes)
+        if precon == 'amg':  # z = M r is a V-cycle (nh_amg.hip); the loop below is the same
+            hierarchy = self._amg_hierarchy(free, mask, *preconargs)
+            z, work = device.empty(n, 'float64'), kernels.pcg_work()
+            init = lambda: kernels.pcg_init(hierarchy.handle, r, z, p, work)
+            iterate = lambda steps: kernels.pcg_iterate(values, rowptr, colidx, self._ncols, amg=hierarchy.handle, z=z, work=work, niter=steps, **csr)
+        else:
+            work = kernels.cg_work()
+            init = lambda: kernels.cg_init(dinv, r, p, work)
+            iterate = lambda steps: kernels.cg_iterate(values, rowptr, colidx, self._ncols, dinv=dinv, work=work, niter=steps, **csr)
         result = (lambda: x) if on_device else (lambda: device.to_host(x))
         stop_rr, it = None, 0
         while True:
             self.cg_iterations = self.iterations = it  # (of the last solve, for whoever wants to know)
             self.spmv(x, alpha=-1., beta=1., b=b, rowmask=mask, y=r)  # the true residual, mask(rhs - A x)
-            kernels.cg_init(dinv, r, p, work)
+            init()
             rr, _ = work[:2].tolist()
             if stop_rr is None:
                 stop_rr = max(atol, rtol * rr ** .5) ** 2  # (the device compares r . r with this number, and so does the host)
@@ -442,8 +474,7 @@ class HipMatrix:
             kernels.cg_stop(work, stop_rr)  # (the iterations enqueued past convergence idle: their r . z would underflow before r . r, a false breakdown)
             while it < maxiter:
                 steps = min(check, maxiter - it)
-                kernels.cg_iterate(values, rowptr, colidx, self._ncols, rowmask=mask, dinv=dinv, x=x, r=r, p=p, q=q, work=work, niter=steps, col32=self._columns(),
-                                   lanes=self.lanes)
+                iterate(steps)
                 it += steps
                 rr, flag = work[:2].tolist()
                 if flag:

@@ -13,9 +13,12 @@
   * for the same twin, restarted GMRES at restart 10, 30 and 100: the time of an Arnoldi step (the mean over a full cycle, whose step j reads j + 1 basis
     vectors four times), the product's share of it and the share of everything else (the Gram-Schmidt kernels, the scalar kernel, the normalisation), the
     model's bytes of that rest, (4 (j + 1) + c) 8 n per step with c = 2 ceil((j + 1) / 8) + 8 passes over w, z, dinv and the new basis vector, over its time as a
-    fraction of 8 TB/s, and steps, wall time and true residual of a Jacobi-GMRES solve under the conditions of the BiCGStab solve.
+    fraction of 8 TB/s, and steps, wall time and true residual of a Jacobi-GMRES solve under the conditions of the BiCGStab solve,
+  * for the smoothed-aggregation AMG preconditioner (precon='amg'): the time of the symbolic and of the numeric phase of its setup, level sizes and operator
+    complexity, one cycle against one masked product, and iterations, wall time and true residual of an AMG-CG solve (with the symbolic phase, and with it
+    cached) beside the Jacobi-CG solve of the same system in the same process.
 
-Usage: python tools/matrix_probe.py [--matrices poisson128,elasticity96,bilinear2048,p2vector32] [--scale 1.0] [--sections spmv,cg,bicgstab,fgmres] [--out FILE]
+Usage: python tools/matrix_probe.py [--matrices poisson128,elasticity96,bilinear2048,bilinear1024,p2vector32] [--scale 1.0] [--sections spmv,cg,bicgstab,fgmres,amg] [--out FILE]
 (--scale shrinks every mesh for a quick look; --sections leaves parts out).  Not run by any test.'''
 import argparse
 import json
@@ -39,6 +42,8 @@ def build(name, scale):
         shape, degree, vector = [n(96)] * 3, 1, True
     elif name == 'bilinear2048':
         shape, degree, vector = [n(2048)] * 2, 1, False
+    elif name == 'bilinear1024':
+        shape, degree, vector = [n(1024)] * 2, 1, False
     elif name == 'p2vector32':
         shape, degree, vector = [n(32)] * 3, 2, True
     else:
@@ -141,6 +146,8 @@ def probe(name, args):
         info['bicgstab'] = probe_bicgstab(A, free, mask, rhs_dev, res0, args)
     if 'fgmres' in args.sections:
         info['fgmres'] = probe_fgmres(A, free, mask, rhs_dev, res0, args)
+    if 'amg' in args.sections:
+        info['amg'] = probe_amg(A, free, mask, rhs_dev, res0, args)
     return info
 
 
@@ -212,6 +219,60 @@ def probe_cg(A, free, mask, rhs_dev, res0, info, args):
     device.synchronize()
     info['solve'].update(wall_ms=(time.perf_counter() - t0) * 1e3, iterations=A.cg_iterations)
     info['solve']['true_relative_residual'] = float(A.spmv(sol, alpha=-1., beta=1., b=rhs_dev, rowmask=mask).norm() / res0.norm())
+
+
+def probe_amg(A, free, mask, rhs_dev, res0, args):
+    '''precon='amg': the symbolic and the numeric phase of the setup (wall clock, synchronised; the numeric one a first and a second time), one cycle
+    against one masked product, and AMG-CG and Jacobi-CG solves of the same system in the same process'''
+    import torch
+    from nutils_amd import amg, device, kernels, matrix
+    values, rowptr, colidx = A.triplet()
+    out = {}
+
+    def clocked(fn):
+        device.synchronize()
+        t0 = time.perf_counter()
+        result = fn()
+        device.synchronize()
+        return result, (time.perf_counter() - t0) * 1e3
+
+    try:
+        levels, out['symbolic_ms'] = clocked(lambda: amg.symbolic(rowptr, colidx, mask != 0, 256))
+    except (matrix.MatrixError, RuntimeError) as e:  # (a product beyond the int32 indices of its plan, or out of memory: recorded, not hidden)
+        return dict(error=f'{type(e).__name__}: {e}')
+    h, out['numeric_first_ms'] = clocked(lambda: amg.Hierarchy(levels, values))
+    h, out['numeric_ms'] = clocked(lambda: amg.Hierarchy(levels, values))
+    out['levels'] = [lv.nfree for lv in levels]
+    out['kinds'] = [lv.kind for lv in levels]
+    nnzs = [lv.colidx.numel() for lv in levels]
+    out['operator_complexity'] = sum(nnzs) / nnzs[0]
+    r = torch.where(mask != 0, torch.from_numpy(numpy.random.default_rng(1).normal(size=A.shape[0])).cuda(), torch.zeros_like(rhs_dev))
+    z = torch.empty_like(r)
+    masked = lambda: A.spmv(r, y=z, rowmask=mask)
+    t_cycle, t_mv = windows([lambda: h.apply(r, z), masked], args.window)
+    out['cycle'] = stats(t_cycle)
+    out['masked_spmv'] = stats(t_mv)
+    out['cycle_over_product'] = out['cycle']['us'] / out['masked_spmv']['us']
+    out['launches_per_cycle'] = 5 * (len(levels) - 1) + 1
+    def solve(precon):
+        try:
+            return A.solve(rhs_dev, constrain=~free, rtol=1e-8, maxiter=args.maxiter, precon=precon), True
+        except matrix.ToleranceNotReached as e:
+            return e.best, False
+
+    A._amg = None
+    runs = {precon: [clocked(lambda: solve(precon))] for precon in ('amg', 'diag')}  # the first 'amg' solve runs the symbolic phase, the later ones find it cached
+    for _ in range(3):  # (alternating)
+        for precon in runs:
+            runs[precon].append(clocked(lambda: solve(precon)))
+    for precon, timed in runs.items():
+        (sol, converged), first = timed[0]
+        res = dict(converged=converged, first_ms=first, wall_ms=float(numpy.median([ms for _, ms in timed[1:]])), spread=(max(ms for _, ms in timed[1:]) - min(ms for _, ms in timed[1:])))
+        solve(precon)
+        res['iterations'] = A.iterations
+        res['true_relative_residual'] = float(A.spmv(sol, alpha=-1., beta=1., b=rhs_dev, rowmask=mask).norm() / res0.norm())
+        out['solve_' + precon] = res
+    return out
 
 
 BICGSTAB_STEPS = 20
@@ -369,7 +430,7 @@ def main():
     ap.add_argument('--window', type=float, default=.3)
     ap.add_argument('--maxiter', type=int, default=20000)
     ap.add_argument('--no-host-solve', action='store_true', help='skip the host BiCGStab of the nonsymmetric twin (minutes for the large matrices)')
-    ap.add_argument('--sections', default='spmv,cg,bicgstab,fgmres', help='the parts of the probe to run')
+    ap.add_argument('--sections', default='spmv,cg,bicgstab,fgmres,amg', help='the parts of the probe to run')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     args.sections = args.sections.split(',')

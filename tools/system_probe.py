@@ -206,6 +206,8 @@ def probe(name, args):
         raise SystemExit(f'unknown workload {name!r}')
     info['linargs'] = linargs
     info['device'] = route(make, arguments, constrain, linargs, True, True, args.reps)
+    if name == 'laplace':  # the same solve under the multigrid preconditioner: the first repetition builds the plan, the later ones reuse it (the median is theirs)
+        info['device_amg'] = route(make, arguments, constrain, dict(linargs, precon='amg'), True, True, args.reps)
     info['host'] = route(make, arguments, constrain, linargs, False, info['device']['size'] <= args.host_solve_dofs, args.reps)
     return info
 
