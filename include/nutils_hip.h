@@ -428,7 +428,9 @@ typedef struct {
   int plane_begin, plane_end;
   const double *verts_dev;   /* [(n0+1)(n1+1)(n2+1)][3]; NULL: x = origin + scale * vertex index */
   double origin[3], scale[3];
-  double gauss_x[2], gauss_w[2]; /* 1-D Gauss points / weights on [0,1] */
+  double gauss_x[2], gauss_w[2]; /* 1-D Gauss points / weights on [0,1].  The points must be symmetric about 1/2 (gauss_x[0] +
+                                    gauss_x[1] = 1 to 1e-14, as those of the 2-point Gauss rule are): the element routine uses it,
+                                    and every entry that takes this struct returns NH_EINVAL for any other rule */
   double kappa;                  /* constant diffusivity */
   double *values_dev;
   const double *unit_matrix_dev; /* uniform geometry only: the 8x8 element matrix from nh_p1hex_unit_matrix (computed once per

@@ -901,6 +901,8 @@ static int fill_p1args(const nh_p1hex_args *a, P1Args &p) {
   NH_REQUIRE(a->shape[0] >= 1 && a->shape[1] >= 1 && a->shape[2] >= 1, "nh_p1hex: empty mesh");
   NH_REQUIRE(0 <= a->layer_begin && a->layer_begin <= a->layer_end && a->layer_end <= a->shape[0], "nh_p1hex: layer range");
   NH_REQUIRE(0 <= a->plane_begin && a->plane_begin <= a->plane_end && a->plane_end <= a->shape[0] + 1, "nh_p1hex: plane range");
+  // the contractions of nh_p1hex_math.inc are written for points symmetric about 1/2 (points.gauss1(2), the only rule the callers pass)
+  NH_REQUIRE(fabs(a->gauss_x[0] + a->gauss_x[1] - 1.) <= 1e-14, "nh_p1hex: gauss_x must be a symmetric 2-point rule (gauss_x[0] + gauss_x[1] = 1)");
   p.n0 = a->shape[0];
   p.n1 = a->shape[1];
   p.n2 = a->shape[2];

@@ -742,19 +742,7 @@ __global__ __launch_bounds__(FUSED_NT_MAX) void k_fused_p1hex(FusK fp) {
 #include "nh_p1hex_math.inc"
 #undef NH_P1HEX_QS
 #undef NH_P1HEX_QM
-    auto entry = [&](int a, int bb) {  // K[a][bb], a <= bb: nine signed table values (+ the mass term), as in nh_p1hex_element.inc
-      const int a0 = a >> 2, a1 = (a >> 1) & 1, a2 = a & 1;
-      const int b0 = bb >> 2, b1 = (bb >> 1) & 1, b2 = bb & 1;
-      const int p0 = a0 + b0, p1 = a1 + b1, p2 = a2 + b2;
-      const double s00 = (a0 == b0) ? 1. : -1., s11 = (a1 == b1) ? 1. : -1., s22 = (a2 == b2) ? 1. : -1.;
-      const double s01 = (a0 == b1) ? 1. : -1., s10 = (b0 == a1) ? 1. : -1.;
-      const double s02 = (a0 == b2) ? 1. : -1., s20 = (b0 == a2) ? 1. : -1.;
-      const double s12 = (a1 == b2) ? 1. : -1., s21 = (b1 == a2) ? 1. : -1.;
-      double k = s00 * R0[p1][p2] + s11 * R1[p0][p2] + s22 * R2[p0][p1] + s01 * W01[b0][a1][p2] + s10 * W01[a0][b1][p2] + s02 * W02[b0][a2][p1] + s20 * W02[a0][b2][p1] +
-                 s12 * W12[b1][a2][p0] + s21 * W12[a1][b2][p0];
-      if (hasm) k += Mm[p0][p1][p2];
-      return k;
-    };
+#include "nh_p1hex_entry.inc"  // entry(a, bb) = K[a][bb], a <= bb
     double K[36];  // upper triangle, row major
     {
       int q = 0;
@@ -1500,6 +1488,7 @@ static bool fused_p1hex_tables(const nh_matrix_args *a, P1Tab *tab, bool *mass, 
   gx[0] = x[0][0], gx[1] = x[0][4];
   gw[0] = w[0] + w[1] + w[2] + w[3], gw[1] = w[4] + w[5] + w[6] + w[7];
   const double tol = 1e-14;
+  if (fabs(gx[0] + gx[1] - 1.) > tol) return false;  // nh_p1hex_math.inc needs points symmetric about 1/2; any other rule takes the general kernel
   for (int q = 0; q < 8; ++q) {
     const int qi[3] = {q >> 2, (q >> 1) & 1, q & 1};
     for (int ax = 0; ax < 3; ++ax)

@@ -56,20 +56,8 @@
 #include "nh_p1hex_math.inc"
 #undef NH_P1HEX_QS
 #undef NH_P1HEX_QM
-        // the 36 entries a <= b of the local matrix: nine signed table values each (+ the mass term)
-        auto entry = [&](int a, int bb) {
-          const int a0 = a >> 2, a1 = (a >> 1) & 1, a2 = a & 1;
-          const int b0 = bb >> 2, b1 = (bb >> 1) & 1, b2 = bb & 1;
-          const int p0 = a0 + b0, p1 = a1 + b1, p2 = a2 + b2;
-          const double s00 = (a0 == b0) ? 1. : -1., s11 = (a1 == b1) ? 1. : -1., s22 = (a2 == b2) ? 1. : -1.;
-          const double s01 = (a0 == b1) ? 1. : -1., s10 = (b0 == a1) ? 1. : -1.;
-          const double s02 = (a0 == b2) ? 1. : -1., s20 = (b0 == a2) ? 1. : -1.;
-          const double s12 = (a1 == b2) ? 1. : -1., s21 = (b1 == a2) ? 1. : -1.;
-          double k = s00 * R0[p1][p2] + s11 * R1[p0][p2] + s22 * R2[p0][p1] + s01 * W01[b0][a1][p2] + s10 * W01[a0][b1][p2]
-                   + s02 * W02[b0][a2][p1] + s20 * W02[a0][b2][p1] + s12 * W12[b1][a2][p0] + s21 * W12[a1][b2][p0];
-          if (hasm) k += Mm[p0][p1][p2];
-          return k;
-        };
+        // the 36 entries a <= b of the local matrix: entry(a, bb)
+#include "nh_p1hex_entry.inc"
         {  // reduce: the accumulated rows of a plane are the vertices of the tile, so every local vertex has a row (no masking)
           // every entry goes to LDS as soon as it is formed: the ds_add_f64 stream overlaps the remaining arithmetic of the same wave
           // (issued in one burst at the end, the 36 atomics of all waves pile up in front of the barrier)

@@ -6,6 +6,9 @@
 // terms, indexed by the pair classes p_d = a_d + b_d) and W01[2][2][3], W02[2][2][3], W12[2][2][3] (off-diagonal terms).
 // Computes: Jacobian columns, metric tensors at the 8 Gauss points, axis-by-axis contractions (DESIGN.md, "P1-hex local matrix
 // by sum factorisation").
+// REQUIRES a 2-point rule that is symmetric about 1/2, g0 + g1 = 1 (points.gauss1(2), the only rule the callers pass): the contractions read
+// n[0][0], c[0][0], c[0][1], c[1][0] and take the other table values from the symmetry.  The host guards it: fill_p1args refuses any other rule,
+// fused_p1hex_tables leaves it to the general kernel.  (The mass block and the Jacobian columns hold for any 2-point rule.)
 {
   // uniform tables (SGPR resident): n[a][q] = N_a(g_q), c[p][q] = n[x][q] n[y][q] with p = x + y, wk = kappa w w w
   const double (&n)[2][2] = p.n;
@@ -83,93 +86,84 @@
         if (hasm) Dm[qa][qb][qc] = p.wm[qa][qb][qc] * NH_P1HEX_QM(qa * 4 + qb * 2 + qc) * fabs(det);
       }
   // ---- axis-by-axis contractions -------------------------------------------------------------------
+  // The rule is symmetric about 1/2 (g0 + g1 = 1), so with al = n[0][0]: n[1][1] = al, n[0][1] = n[1][0] = 1 - al, and c[1][0] = c[1][1],
+  // c[2][0] = c[0][1], c[2][1] = c[0][0].  A 2 -> 2 interpolation stage is then a difference and two fma (3 instead of 4 instructions):
+  //   n[0][0] u0 + n[0][1] u1 = u1 + al (u0 - u1),   n[1][0] u0 + n[1][1] u1 = u0 - al (u0 - u1)
+  // and a 2 -> 3 pair-class stage takes 5 instead of 6: the middle class has one coefficient, the last is the first with x and y swapped:
+  //   out0 = c00 x + c01 y,   out1 = c10 (x + y),   out2 = c01 x + c00 y = (c00 + c01) (x + y) - out0
+  const double al = n[0][0], nal = -al, c00 = c[0][0], c01 = c[0][1], c10 = c[1][0], cs = c00 + c01;
+#define NH_P1HEX_LERP(o0, o1, u0, u1) \
+  {                                   \
+    const double d_ = (u0) - (u1);    \
+    o0 = fma(al, d_, u1);             \
+    o1 = fma(nal, d_, u0);            \
+  }
+#define NH_P1HEX_PAIR(o0, o1, o2, x, y) \
+  {                                     \
+    const double s_ = (x) + (y);        \
+    o0 = fma(c00, x, c01 * (y));        \
+    o1 = c10 * s_;                      \
+    o2 = fma(cs, s_, -(o0));            \
+  }
   {
     double U[2][3];
 #pragma unroll
-    for (int x = 0; x < 2; ++x)
+    for (int x = 0; x < 2; ++x) NH_P1HEX_PAIR(U[x][0], U[x][1], U[x][2], D0[x][0], D0[x][1])
 #pragma unroll
-      for (int pp = 0; pp < 3; ++pp) U[x][pp] = c[pp][0] * D0[x][0] + c[pp][1] * D0[x][1];
+    for (int p2 = 0; p2 < 3; ++p2) NH_P1HEX_PAIR(R0[0][p2], R0[1][p2], R0[2][p2], U[0][p2], U[1][p2])
 #pragma unroll
-    for (int p1 = 0; p1 < 3; ++p1)
+    for (int x = 0; x < 2; ++x) NH_P1HEX_PAIR(U[x][0], U[x][1], U[x][2], D1[x][0], D1[x][1])
 #pragma unroll
-      for (int p2 = 0; p2 < 3; ++p2) R0[p1][p2] = c[p1][0] * U[0][p2] + c[p1][1] * U[1][p2];
+    for (int p2 = 0; p2 < 3; ++p2) NH_P1HEX_PAIR(R1[0][p2], R1[1][p2], R1[2][p2], U[0][p2], U[1][p2])
 #pragma unroll
-    for (int x = 0; x < 2; ++x)
+    for (int x = 0; x < 2; ++x) NH_P1HEX_PAIR(U[x][0], U[x][1], U[x][2], D2[x][0], D2[x][1])
 #pragma unroll
-      for (int pp = 0; pp < 3; ++pp) U[x][pp] = c[pp][0] * D1[x][0] + c[pp][1] * D1[x][1];
-#pragma unroll
-    for (int p0 = 0; p0 < 3; ++p0)
-#pragma unroll
-      for (int p2 = 0; p2 < 3; ++p2) R1[p0][p2] = c[p0][0] * U[0][p2] + c[p0][1] * U[1][p2];
-#pragma unroll
-    for (int x = 0; x < 2; ++x)
-#pragma unroll
-      for (int pp = 0; pp < 3; ++pp) U[x][pp] = c[pp][0] * D2[x][0] + c[pp][1] * D2[x][1];
-#pragma unroll
-    for (int p0 = 0; p0 < 3; ++p0)
-#pragma unroll
-      for (int p1 = 0; p1 < 3; ++p1) R2[p0][p1] = c[p0][0] * U[0][p1] + c[p0][1] * U[1][p1];
+    for (int p1 = 0; p1 < 3; ++p1) NH_P1HEX_PAIR(R2[0][p1], R2[1][p1], R2[2][p1], U[0][p1], U[1][p1])
   }
   {
-    // W01[b0][a1][p2] = sum_ga c[p2][ga] sum_be n[a1][be] sum_al n[b0][al] M01[al][be][ga]   (two-term axes first: 16+16+24 ops)
+    // W01[b0][a1][p2] = sum_ga c[p2][ga] sum_be n[a1][be] sum_al n[b0][al] M01[al][be][ga]   (two-term axes first: 12+12+20 ops)
     double V[2][2][2], V2[2][2][2];
 #pragma unroll
-    for (int b0 = 0; b0 < 2; ++b0)
+    for (int be = 0; be < 2; ++be)
 #pragma unroll
-      for (int be = 0; be < 2; ++be)
-#pragma unroll
-        for (int ga = 0; ga < 2; ++ga) V[b0][be][ga] = n[b0][0] * M01[0][be][ga] + n[b0][1] * M01[1][be][ga];
+      for (int ga = 0; ga < 2; ++ga) NH_P1HEX_LERP(V[0][be][ga], V[1][be][ga], M01[0][be][ga], M01[1][be][ga])
 #pragma unroll
     for (int b0 = 0; b0 < 2; ++b0)
 #pragma unroll
-      for (int a1 = 0; a1 < 2; ++a1)
-#pragma unroll
-        for (int ga = 0; ga < 2; ++ga) V2[b0][a1][ga] = n[a1][0] * V[b0][0][ga] + n[a1][1] * V[b0][1][ga];
+      for (int ga = 0; ga < 2; ++ga) NH_P1HEX_LERP(V2[b0][0][ga], V2[b0][1][ga], V[b0][0][ga], V[b0][1][ga])
 #pragma unroll
     for (int b0 = 0; b0 < 2; ++b0)
 #pragma unroll
-      for (int a1 = 0; a1 < 2; ++a1)
-#pragma unroll
-        for (int pp = 0; pp < 3; ++pp) W01[b0][a1][pp] = c[pp][0] * V2[b0][a1][0] + c[pp][1] * V2[b0][a1][1];
+      for (int a1 = 0; a1 < 2; ++a1) NH_P1HEX_PAIR(W01[b0][a1][0], W01[b0][a1][1], W01[b0][a1][2], V2[b0][a1][0], V2[b0][a1][1])
     // W02[b0][a2][p1] = sum_be c[p1][be] sum_ga n[a2][ga] sum_al n[b0][al] M02[al][be][ga]
 #pragma unroll
-    for (int b0 = 0; b0 < 2; ++b0)
+    for (int be = 0; be < 2; ++be)
 #pragma unroll
-      for (int be = 0; be < 2; ++be)
-#pragma unroll
-        for (int ga = 0; ga < 2; ++ga) V[b0][be][ga] = n[b0][0] * M02[0][be][ga] + n[b0][1] * M02[1][be][ga];
+      for (int ga = 0; ga < 2; ++ga) NH_P1HEX_LERP(V[0][be][ga], V[1][be][ga], M02[0][be][ga], M02[1][be][ga])
 #pragma unroll
     for (int b0 = 0; b0 < 2; ++b0)
 #pragma unroll
-      for (int a2 = 0; a2 < 2; ++a2)
-#pragma unroll
-        for (int be = 0; be < 2; ++be) V2[b0][a2][be] = n[a2][0] * V[b0][be][0] + n[a2][1] * V[b0][be][1];
+      for (int be = 0; be < 2; ++be) NH_P1HEX_LERP(V2[b0][0][be], V2[b0][1][be], V[b0][be][0], V[b0][be][1])
 #pragma unroll
     for (int b0 = 0; b0 < 2; ++b0)
 #pragma unroll
-      for (int a2 = 0; a2 < 2; ++a2)
-#pragma unroll
-        for (int pp = 0; pp < 3; ++pp) W02[b0][a2][pp] = c[pp][0] * V2[b0][a2][0] + c[pp][1] * V2[b0][a2][1];
+      for (int a2 = 0; a2 < 2; ++a2) NH_P1HEX_PAIR(W02[b0][a2][0], W02[b0][a2][1], W02[b0][a2][2], V2[b0][a2][0], V2[b0][a2][1])
     // W12[b1][a2][p0] = sum_al c[p0][al] sum_ga n[a2][ga] sum_be n[b1][be] M12[al][be][ga]
 #pragma unroll
-    for (int b1 = 0; b1 < 2; ++b1)
+    for (int al_ = 0; al_ < 2; ++al_)
 #pragma unroll
-      for (int al = 0; al < 2; ++al)
-#pragma unroll
-        for (int ga = 0; ga < 2; ++ga) V[b1][al][ga] = n[b1][0] * M12[al][0][ga] + n[b1][1] * M12[al][1][ga];
+      for (int ga = 0; ga < 2; ++ga) NH_P1HEX_LERP(V[0][al_][ga], V[1][al_][ga], M12[al_][0][ga], M12[al_][1][ga])
 #pragma unroll
     for (int b1 = 0; b1 < 2; ++b1)
 #pragma unroll
-      for (int a2 = 0; a2 < 2; ++a2)
-#pragma unroll
-        for (int al = 0; al < 2; ++al) V2[b1][a2][al] = n[a2][0] * V[b1][al][0] + n[a2][1] * V[b1][al][1];
+      for (int al_ = 0; al_ < 2; ++al_) NH_P1HEX_LERP(V2[b1][0][al_], V2[b1][1][al_], V[b1][al_][0], V[b1][al_][1])
 #pragma unroll
     for (int b1 = 0; b1 < 2; ++b1)
 #pragma unroll
-      for (int a2 = 0; a2 < 2; ++a2)
-#pragma unroll
-        for (int pp = 0; pp < 3; ++pp) W12[b1][a2][pp] = c[pp][0] * V2[b1][a2][0] + c[pp][1] * V2[b1][a2][1];
+      for (int a2 = 0; a2 < 2; ++a2) NH_P1HEX_PAIR(W12[b1][a2][0], W12[b1][a2][1], W12[b1][a2][2], V2[b1][a2][0], V2[b1][a2][1])
   }
+#undef NH_P1HEX_LERP
+#undef NH_P1HEX_PAIR
   if (hasm) {
     // mass term: M[a][b] = sum_q w_q |det J_q| N_a N_b = Mm[a0+b0][a1+b1][a2+b2], contracted axis by axis with c[p][q] = n[x][q] n[y][q]
     double t1[2][2][3], t2[2][3][3];
