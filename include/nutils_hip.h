@@ -766,6 +766,13 @@ int nh_gmres_update(int64_t n, int restart, const double *dinv_dev, const double
  * geometry a function of sizes only, repeated calls bit-identical, argument errors NH_EINVAL before a launch, empty sizes no launch.
  * nh_segment_dot: out[s] = sum of a[ia[k]] * b[ib[k]] over k = ptr[s] .. ptr[s + 1] - 1, s < nseg; b_dev NULL: the plain segment sum of a[ia[k]].  ptr int64
  * [nseg + 1], ia / ib int32 [nprod], nprod = ptr[nseg].  Lanes per segment follow from the mean segment length by the rule of nh_csr_lanes.
+ * nh_aggregate_qr: the thin QR of a near-nullspace B_dev [n x k] row-major, 1 <= k <= 6, on the rows of every aggregate: aggregate a < nagg has the rows
+ * midx[mptr[a]] .. midx[mptr[a + 1] - 1] (mptr int64 [nagg + 1], midx int32 [nmembers], nmembers = mptr[nagg]; every row below n, in at most one aggregate).
+ * Q_dev [n x k] row-major gets the orthonormal columns on the rows of each aggregate and 0 on rows in none; Rc_dev [nagg k x k] row-major gets block a =
+ * R of aggregate a, upper triangular with a non-negative diagonal, so that Q R = B on the aggregate's rows.  Columns left to right: n0 = |b_j|, two passes
+ * of modified Gram-Schmidt against q_0 .. q_(j-1) with R[l][j] the sum of the two coefficients, n1 = |b_j| afterwards; n1 <= 2^-26 n0 drops the column
+ * (q_j = 0 and R[j][j] = 0 exactly, R[l][j] kept), otherwise q_j /= n1 and R[j][j] = n1.  Lanes per aggregate follow from the mean size by the rule of
+ * nh_csr_lanes.  Q_dev must not be B_dev.
  * nh_csr_jacobi: y = x + w (b - A x) on the rows the mask keeps, 0 on the others, in one launch; y must not be x.
  * nh_amg is a hierarchy made of level descriptions; like nh_csr it holds views and owns no device memory, and every vector of a description is the caller's
  * to allocate and to keep.  Level l < nlevels - 1 has kind NH_AMG_COARSEN: A (its matrix), rowmask_dev (level 0 only; NULL: all rows), w_dev = omega / diag
@@ -795,6 +802,8 @@ typedef struct {
 
 int nh_segment_dot(int64_t nseg, const int64_t *ptr_dev, const int32_t *ia_dev, const int32_t *ib_dev, const double *a_dev, const double *b_dev, int64_t nprod,
                    double *out_dev, void *stream);
+int nh_aggregate_qr(int64_t nagg, const int64_t *mptr_dev, const int32_t *midx_dev, int64_t nmembers, int k, int64_t n, const double *B_dev, double *Q_dev,
+                    double *Rc_dev, void *stream);
 int nh_csr_jacobi(const nh_csr *A, const double *x_dev, const double *w_dev, const double *b_dev, const unsigned char *rowmask_dev, double *y_dev, void *stream);
 int nh_amg_create(const nh_amg_level *levels, int nlevels, nh_amg **out);
 int nh_amg_free(nh_amg *amg);

@@ -25,7 +25,18 @@ termination  a level with at most ``coarse`` free dofs is solved densely (numpy.
 cycle        V(sweeps, sweeps): x = omega dinv b, further sweeps x += omega dinv (b - A x), r = b - A x, x += P cycle(R r), `sweeps` sweeps more.  Equal
              pre- and post-smoothing with omega < 2 / rho keeps the cycle symmetric positive definite, which CG needs.
 
-The constant is the only near-nullspace vector: elasticity gets a valid preconditioner, not an optimal one.'''
+Without further arguments the constant is the only near-nullspace vector, which is right for scalar problems; elasticity then gets a valid preconditioner,
+not an optimal one.  A vector problem hands its near-nullspace B [n x k], k <= 6, to the setup (``preconargs=dict(nullspace=B)``; for elasticity the
+rigid-body modes, ``rigid_body_modes``), and the algorithm becomes:
+
+nodes        on level 0 every dof is a node, on a coarse level node = dof // k; the aggregation runs on the graph of nodes (I next to J where an entry of A_f
+             joins a dof of one to a dof of the other), and a dof is in the aggregate of its node.
+prolongator  T has k columns per aggregate: on the rows of aggregate a, the columns a k .. a k + k - 1 hold the Q of the thin QR of B on those rows
+             (nh_aggregate_qr: Gram-Schmidt in two passes, a column that vanishes against the earlier ones is dropped: zero in Q, a zero diagonal entry in R).
+             The triangles R, stacked, are the B of the coarse level, which has k dofs per aggregate and no mask.  P, R = P^T and A_c as above.
+dropped      the coarse dof of a dropped column has a zero column of P, a zero row and column of A_c: dinv = 0 there, the smoother leaves it alone and the
+             pseudo-inverse of the dense level ignores it.
+termination  at most ``coarse`` free dofs: dense; as many aggregates as free nodes: z = dinv b, exact for k = 1 and symmetric positive semidefinite always.'''
 
 import numpy
 
@@ -101,6 +112,11 @@ def aggregate(rowptr, colidx, free=None):
     return agg, int(root.sum()), rounds
 
 
+def _check_nprod(nprod):
+    if nprod >= 1 << 31:
+        raise _error()(f'a sparse product of {nprod} terms exceeds the int32 indices of its plan')
+
+
 class Plan:
     '''expand-sort-compress plan of a sparse product: segment s sums products ptr[s] .. ptr[s + 1] - 1, product k = a[ia[k]] * b[ib[k]] (ib None: a[ia[k]]);
     rows / cols: the output entry of each segment, sorted by (row, col)'''
@@ -108,8 +124,7 @@ class Plan:
     def __init__(self, out_rows, out_cols, ncols, ia, ib):
         torch = _torch()
         nprod = ia.numel()
-        if nprod >= 1 << 31:
-            raise _error()(f'a sparse product of {nprod} terms exceeds the int32 indices of its plan')
+        _check_nprod(nprod)
         key, order = torch.sort(out_rows * ncols + out_cols, stable=True)
         ukey, counts = torch.unique_consecutive(key, return_counts=True)
         self.ptr = torch.zeros(ukey.numel() + 1, dtype=torch.int64, device=ia.device)
@@ -125,6 +140,7 @@ def _expand(index, ptr):
     '''for every i and every position m of ptr[index[i]] .. ptr[index[i] + 1] - 1: (i, m), i ascending and m ascending within i'''
     torch = _torch()
     count = ptr[index + 1] - ptr[index]
+    _check_nprod(int(count.sum()))  # (before the lists are made, not after: they are what runs out of memory)
     src = torch.repeat_interleave(torch.arange(index.numel(), dtype=torch.int64, device=index.device), count)
     start = torch.cumsum(count, 0) - count
     return src, ptr[index][src] + torch.arange(src.numel(), dtype=torch.int64, device=index.device) - start[src]
@@ -134,23 +150,53 @@ class Level:
     '''What the symbolic phase knows of a level: n dofs, nfree of them free (`free`: bool tensor, None: all), the CSR pattern (rowptr, colidx) and `kind`
     ('coarsen', 'dense' or 'diagonal').  Of a coarsened level also: agg, nc; the pattern of P (prowptr, prow, pcol) with tind = T on it; the permutation
     rperm that takes the values of P to those of R, and R's pattern (rrowptr, rcol); the plans at (A T), ap (A P) and rap (R (A P)), whose output entries
-    are the patterns of P, A P and A_c.'''
+    are the patterns of P, A P and A_c.  With a near-nullspace of k vectors (`k`; None without): nodesize (1 on level 0, k below: the dofs of a node), nagg,
+    nc = nagg k, the free dofs aggregate by aggregate (mptr, midx), the plan `at` with two factors, a[e] T[acol[e], j] on T's value array [n x k], and
+    instead of tind the map tmap from the entries of P into that array (-1: none).'''
+
+
+def _node_graph(rowptr, colidx, size):
+    '''the CSR pattern of the graph whose node I is the dofs I size .. I size + size - 1: I next to J where an entry joins a dof of one to a dof of the other'''
+    torch = _torch()
+    nnodes = (rowptr.numel() - 1) // size
+    key = torch.unique(torch.div(_rows(rowptr), size, rounding_mode='floor') * nnodes + torch.div(colidx, size, rounding_mode='floor'))  # (sorted)
+    rows = torch.div(key, nnodes, rounding_mode='floor')
+    return _rowptr(rows, nnodes), key - rows * nnodes
 
 
 def _coarsen(lv):
     torch = _torch()
-    rowptr, colidx, free, n = lv.rowptr, lv.colidx, lv.free, lv.n
-    lv.agg, lv.nc, lv.rounds = aggregate(rowptr, colidx, free)
-    nc = lv.nc
+    rowptr, colidx, free, n, nk = lv.rowptr, lv.colidx, lv.free, lv.n, lv.k
+    if nk is None or lv.nodesize == 1:
+        lv.agg, lv.nagg, lv.rounds = aggregate(rowptr, colidx, free)
+    else:  # a coarse level of a hierarchy with a near-nullspace: the k dofs of a node stay together
+        nodeagg, lv.nagg, lv.rounds = aggregate(*_node_graph(rowptr, colidx, lv.nodesize))
+        lv.agg = nodeagg[torch.div(torch.arange(n, dtype=torch.int64, device=rowptr.device), lv.nodesize, rounding_mode='floor')]
+    nc = lv.nc = lv.nagg * (nk or 1)
     rows = _rows(rowptr)
     k = torch.arange(colidx.numel(), dtype=torch.int64, device=colidx.device)
     if free is not None:
         k = k[free[rows] & free[colidx]]  # the entries of A_f
     arow, acol = rows[k], colidx[k]
-    lv.at = Plan(arow, lv.agg[acol], nc, k, None)
+    if nk is None:
+        lv.at = Plan(arow, lv.agg[acol], nc, k, None)
+    else:
+        if n * nk >= 1 << 31:
+            raise _error()(f'{n} dofs times {nk} near-nullspace vectors exceed the int32 indices of the plans')
+        _check_nprod(k.numel() * nk)
+        dofs = torch.arange(n, dtype=torch.int64, device=rowptr.device) if free is None else torch.nonzero(free).reshape(-1)
+        sagg, order = torch.sort(lv.agg[dofs], stable=True)  # the free dofs aggregate by aggregate, ascending within one: what nh_aggregate_qr walks
+        lv.mptr, lv.midx = _rowptr(sagg, lv.nagg), dofs[order].to(torch.int32)
+        j = torch.arange(nk, dtype=torch.int64, device=rowptr.device).repeat(k.numel())
+        ke, re, ce = (t.repeat_interleave(nk) for t in (k, arow, acol))
+        lv.at = Plan(re, lv.agg[ce] * nk + j, nc, ke, ce * nk + j)  # (A T)[i, agg(c) k + j] = sum over the entries (i, c) of a[e] T[c, j], T = Q [n x k]
     lv.prow, lv.pcol = lv.at.rows, lv.at.cols
     lv.prowptr = _rowptr(lv.prow, n)
-    lv.tind = (lv.pcol == lv.agg[lv.prow]).to(torch.float64)
+    if nk is None:
+        lv.tind = (lv.pcol == lv.agg[lv.prow]).to(torch.float64)
+    else:  # where an entry of P finds its T in the value array Q, -1: T has none there
+        block = torch.div(lv.pcol, nk, rounding_mode='floor')
+        lv.tmap = torch.where(block == lv.agg[lv.prow], lv.prow * nk + (lv.pcol - block * nk), -1)
     src, m = _expand(acol, lv.prowptr)
     lv.ap = Plan(arow[src], lv.pcol[m], nc, k[src], m)
     aprowptr = _rowptr(lv.ap.rows, n)
@@ -177,9 +223,10 @@ def _dense_block(lv):
         lv.idx32 = torch.nonzero(lv.free).reshape(-1).to(torch.int32)
 
 
-def symbolic(rowptr, colidx, free=None, coarse=256):
+def symbolic(rowptr, colidx, free=None, coarse=256, nullspace=None):
     '''The levels of the hierarchy of a pattern and a mask (`free`: bool tensor, True on free dofs; None: all): a list of `Level`, the last of which is
-    'dense' or 'diagonal'.  No value is read.'''
+    'dense' or 'diagonal'.  `nullspace`: the number k of near-nullspace vectors the numeric phase will be given (None: the constant, on every level).  No
+    value is read.'''
     torch = _torch()
     levels = []
     while True:
@@ -187,6 +234,7 @@ def symbolic(rowptr, colidx, free=None, coarse=256):
         lv.rowptr, lv.colidx, lv.free = rowptr, colidx, free
         lv.n = rowptr.numel() - 1
         lv.nfree = lv.n if free is None else int(free.sum())
+        lv.k, lv.nodesize = nullspace, 1 if nullspace is None or not levels else nullspace
         if lv.n > 0x7fffffff:
             raise _error()(f'{lv.n} dofs exceed the 32 bits the priorities of the aggregation keep for the index')
         lv.col32 = colidx.to(torch.int32)  # what the products of the cycle read (12 instead of 16 bytes per entry)
@@ -197,47 +245,94 @@ def symbolic(rowptr, colidx, free=None, coarse=256):
             _dense_block(lv)
             return levels
         rowptr, colidx = _coarsen(lv)
-        if lv.nc == lv.nfree:  # no edges: a diagonal matrix
+        if lv.nagg * lv.nodesize == lv.nfree:  # as many aggregates as free nodes, no edges: a diagonal matrix (with a near-nullspace of k > 1: diagonal blocks)
             lv.kind = 'diagonal'
             return levels
         lv.kind = 'coarsen'
         free = None
 
 
-def check_args(preconargs):
-    '''(coarse, sweeps) of `preconargs`, validated'''
+MAX_NULLSPACE = 6  # the QR kernel's limit (nh_amg.hip): the rigid-body modes in 3-D
+
+
+def check_args(preconargs, n=None):
+    '''(coarse, sweeps, nullspace) of `preconargs`, validated; nullspace: None, or a float64 host array or device tensor of shape (n, k), n the size of the
+    matrix when given'''
     from .matrix import MatrixError
     args = dict(preconargs or {})
-    coarse, sweeps = args.pop('coarse', 256), args.pop('sweeps', 1)
+    coarse, sweeps, B = args.pop('coarse', 256), args.pop('sweeps', 1), args.pop('nullspace', None)
     if args:
-        raise MatrixError(f"invalid arguments {sorted(args)} for the 'amg' preconditioner: 'coarse' and 'sweeps'")
+        raise MatrixError(f"invalid arguments {sorted(args)} for the 'amg' preconditioner: 'coarse', 'sweeps' and 'nullspace'")
     isint = lambda v: isinstance(v, (int, numpy.integer)) and not isinstance(v, bool)
     if not (isint(coarse) and 1 <= coarse <= MAX_COARSE):
         raise MatrixError(f'amg: coarse must be an integer between 1 and {MAX_COARSE}, got {coarse!r}')
     if not (isint(sweeps) and sweeps >= 1):
         raise MatrixError(f'amg: sweeps must be an integer of at least 1, got {sweeps!r}')
-    return int(coarse), int(sweeps)
+    if B is not None:
+        tensor = type(B).__module__.split('.')[0] == 'torch'
+        if not tensor:
+            try:
+                B = numpy.asarray(B)
+            except Exception:
+                raise MatrixError(f'amg: nullspace must be an array of shape (n, k), got {type(B).__name__}') from None
+        if str(B.dtype).split('.')[-1] != 'float64':
+            raise MatrixError(f'amg: nullspace must be float64, got {B.dtype}')
+        if B.ndim == 1:
+            B = B.reshape(-1, 1)
+        if B.ndim != 2 or (n is not None and B.shape[0] != n):
+            raise MatrixError(f'amg: nullspace must have the shape (n, k) or (n,)' + ('' if n is None else f' with n = {n}') + f', got {tuple(B.shape)}')
+        if not 1 <= B.shape[1] <= MAX_NULLSPACE:
+            raise MatrixError(f'amg: nullspace must have between 1 and {MAX_NULLSPACE} vectors, got k = {B.shape[1]}')
+        if not bool(_torch().isfinite(B).all() if tensor else numpy.isfinite(B).all()):
+            raise MatrixError('amg: nullspace has non-finite entries')
+    return int(coarse), int(sweeps), B
+
+
+def rigid_body_modes(coords):
+    '''The near-nullspace of linear elasticity from the node coordinates `coords` [nnodes x d], d = 2 or 3: a host array [nnodes d x d (d + 1) / 2] whose
+    columns are the d translations and then the rotations ((-y, x) in 2-D; about the x, y and z axis in 3-D), in the dof layout of a vector field
+    (`function.field`: dof = node d + component).'''
+    coords = numpy.asarray(coords, dtype=float)
+    if coords.ndim != 2 or coords.shape[1] not in (2, 3):
+        raise _error()(f'rigid_body_modes: coords must have the shape (nnodes, 2) or (nnodes, 3), got {coords.shape}')
+    nnodes, d = coords.shape
+    B = numpy.zeros((nnodes, d, d * (d + 1) // 2))
+    for c in range(d):
+        B[:, c, c] = 1.
+    if d == 2:
+        B[:, 0, 2], B[:, 1, 2] = -coords[:, 1], coords[:, 0]
+    else:
+        for axis in range(3):  # e_axis x r
+            p, q = (axis + 1) % 3, (axis + 2) % 3
+            B[:, q, 3 + axis], B[:, p, 3 + axis] = coords[:, p], -coords[:, q]
+    return B.reshape(nnodes * d, -1)
 
 
 class Hierarchy:
     '''The numeric phase on the device: the values of every level from those of the finest (`values`, on the pattern of `levels[0]`), and the handle of the
     cycle.  `levels`: of `symbolic`, on device tensors.  Per level `self.data[l]` keeps what the cycle reads: values, dinv, and for a coarsened level rho,
-    omega (0-dim device tensors), w = omega dinv, pvalues, rvalues; for a dense level ainv.'''
+    omega (0-dim device tensors), w = omega dinv, pvalues, rvalues; for a dense level ainv.  `nullspace`: the near-nullspace of level 0, a float64 device
+    tensor [n x k], for levels of ``symbolic(..., nullspace=k)``; a coarsened level then keeps its own as B, the values of T as q [n x k], and hands the
+    triangles of the aggregates' QR on as the B of the next.'''
 
-    def __init__(self, levels, values, sweeps=1):
+    def __init__(self, levels, values, sweeps=1, nullspace=None):
         from . import device, kernels
         from .matrix import MatrixError, spmv_lanes
         torch = _torch()
         self.levels, self.data = levels, []
         descriptions = []
+        B, nk = nullspace, levels[0].k
+        if (nk is None) != (B is None) or (B is not None and tuple(B.shape) != (levels[0].n, nk)):
+            raise MatrixError(f'amg: the levels were made for a near-nullspace of {nk} vectors, the one given has the shape {None if B is None else tuple(B.shape)}')
         for l, lv in enumerate(levels):
             d = Level()
             self.data.append(d)
-            d.values = values
+            d.values, d.B = values, B
             lanes = spmv_lanes(lv.n, lv.colidx.numel())
             diag = kernels.csr_diagonal(values, lv.rowptr, lv.colidx, lv.n, col32=lv.col32)
             keep = torch.ones_like(diag, dtype=torch.bool) if lv.free is None else lv.free
-            if bool(((diag == 0) & keep).any()):
+            # (below level 0 of a hierarchy with a near-nullspace a zero diagonal entry is the coarse dof of a dropped column, a zero row and column: dinv = 0 there)
+            if (nk is None or l == 0) and bool(((diag == 0) & keep).any()):
                 raise MatrixError("building 'amg' preconditioner: diagonal has zero entries")
             d.dinv = (1. / diag).masked_fill(~keep | (diag == 0), 0.)
             d.b, d.x = (None, None) if l == 0 else (device.empty(lv.n, 'float64'), device.empty(lv.n, 'float64'))
@@ -258,8 +353,14 @@ class Hierarchy:
             d.rho = (absrow * d.dinv).max()
             d.omega = 4. / (3. * d.rho)
             d.w = d.omega * d.dinv
-            d.atvalues = kernels.segment_dot(lv.at, values)
-            d.pvalues = lv.tind - d.w[lv.prow] * d.atvalues
+            if nk is None:
+                d.atvalues = kernels.segment_dot(lv.at, values)
+                d.pvalues = lv.tind - d.w[lv.prow] * d.atvalues
+            else:
+                d.q, B = kernels.aggregate_qr(lv.mptr, lv.midx, nk, B)
+                flat = d.q.reshape(-1)
+                d.atvalues = kernels.segment_dot(lv.at, values, flat)
+                d.pvalues = flat[lv.tmap.clamp(min=0)].masked_fill(lv.tmap < 0, 0.) - d.w[lv.prow] * d.atvalues
             d.rvalues = d.pvalues[lv.rperm]
             d.apvalues = kernels.segment_dot(lv.ap, values, d.pvalues)
             d.t, d.r = device.empty(lv.n, 'float64'), device.empty(lv.n, 'float64')

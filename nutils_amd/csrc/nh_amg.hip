@@ -7,6 +7,9 @@
 //     products have been listed and sorted by output entry beforehand.  L lanes own a segment, consecutive lane groups take consecutive segments (so a
 //     wave reads one contiguous span of the index arrays), segments longer than L are walked in strides of L and folded with __shfl_xor: the mapping
 //     of k_csr_spmv.  It evaluates A T, A P and R (A P) of every level.
+//   * k_aggregate_qr<L>: the aggregate-wise thin QR of a near-nullspace B [n x k], k <= 6, by Gram-Schmidt in two passes: Q [n x k] holds the values of the
+//     tentative prolongator, the triangles R are the near-nullspace of the next level.  L lanes own an aggregate (chosen from the mean size as above), rows
+//     strided over them, norms and dots folded with __shfl_xor.  Once per hierarchy build.
 //   * k_jacobi<L, Idx>: y = x + w (b - A x) on the rows the mask keeps, 0 elsewhere, in one launch (k_csr_spmv with another epilogue; y != x).
 //   * k_scale: y = w b, the sweep that starts from zero, and the solve of a diagonal terminal level.
 //   * k_dense: z = Ainv b for the coarsest level, one workgroup, a wave per row, lanes over the columns.
@@ -56,6 +59,94 @@ __global__ __launch_bounds__(WG) void k_segment_dot(i64 nseg, const i64 *__restr
 #pragma unroll
     for (int o = L >> 1; o; o >>= 1) s += __shfl_xor(s, o, L);
     if (live && lane == 0) out[seg] = s;
+  }
+}
+
+constexpr int QR_MAXK = 6;
+
+template <int L>
+__device__ __forceinline__ double group_sum(double s) {
+#pragma unroll
+  for (int o = L >> 1; o; o >>= 1) s += __shfl_xor(s, o, L);
+  return s;  // (the same bits on every lane of the group: each fold adds the same two numbers)
+}
+
+// Thin QR of B on the rows of every aggregate.  L lanes own an aggregate, its rows midx[mptr[a]] .. are strided over them; Q is the working storage (a lane
+// only ever revisits its own rows, what crosses lanes goes through the folds), every control decision around a fold is uniform over the wave (k is, and a
+// dropped column changes values, not the path).  Column j: n0 from B; the second Gram-Schmidt pass against q_0 .. q_(j-1), one after the other (the first
+// was made when each of them was finished); n1; drop or normalise; and in the same pass over the rows the k - j - 1 dots of q_j with the columns to come,
+// whose first pass that is.  Lane 0 keeps R in Rc: the first coefficient is stored, the second added to it.
+template <int L>
+__global__ __launch_bounds__(WG) void k_aggregate_qr(i64 nagg, const i64 *__restrict__ mptr, const int32_t *__restrict__ midx, int k, const double *__restrict__ B,
+                                                     double *__restrict__ Q, double *__restrict__ Rc) {
+  constexpr int G = WG / L;
+  const int lane = threadIdx.x & (L - 1);
+  for (i64 base = (i64)blockIdx.x * G; base < nagg; base += (i64)gridDim.x * G) {  // (uniform trip count: every lane takes part in the folds)
+    const i64 a = base + threadIdx.x / L;
+    const bool live = a < nagg;
+    const i64 m0 = live ? mptr[a] + lane : 0, m1 = live ? mptr[a + 1] : 0;
+    const bool writer = live && lane == 0;
+    double *R = Rc + a * k * k;
+    for (i64 m = m0; m < m1; m += L) {
+      const i64 i = (i64)midx[m] * k;
+      for (int j = 0; j < k; ++j) Q[i + j] = B[i + j];
+    }
+    for (int j = 0; j < k; ++j) {
+      double s = 0;
+      for (i64 m = m0; m < m1; m += L) {
+        const double v = B[(i64)midx[m] * k + j];
+        s += v * v;
+      }
+      const double n0 = sqrt(group_sum<L>(s));
+      for (int l = 0; l < j; ++l) {
+        double c = 0;
+        for (i64 m = m0; m < m1; m += L) {
+          const i64 i = (i64)midx[m] * k;
+          c += Q[i + l] * Q[i + j];
+        }
+        c = group_sum<L>(c);
+        for (i64 m = m0; m < m1; m += L) {
+          const i64 i = (i64)midx[m] * k;
+          Q[i + j] -= c * Q[i + l];
+        }
+        if (writer) R[l * k + j] += c;
+      }
+      s = 0;
+      for (i64 m = m0; m < m1; m += L) {
+        const double v = Q[(i64)midx[m] * k + j];
+        s += v * v;
+      }
+      const double n1 = sqrt(group_sum<L>(s));
+      const bool keep = n1 > 0x1p-26 * n0;  // below a relative sqrt(u) nothing of the column is left that is not rounding
+      double c[QR_MAXK - 1];
+#pragma unroll
+      for (int t = 0; t < QR_MAXK - 1; ++t) c[t] = 0;
+      for (i64 m = m0; m < m1; m += L) {
+        const i64 i = (i64)midx[m] * k;
+        const double q = keep ? Q[i + j] / n1 : 0.;
+        Q[i + j] = q;
+#pragma unroll
+        for (int t = 0; t < QR_MAXK - 1; ++t)
+          if (j + 1 + t < k) c[t] += q * Q[i + j + 1 + t];
+      }
+#pragma unroll
+      for (int t = 0; t < QR_MAXK - 1; ++t)
+        if (j + 1 + t < k) c[t] = group_sum<L>(c[t]);
+      for (i64 m = m0; m < m1; m += L) {
+        const i64 i = (i64)midx[m] * k;
+        const double q = Q[i + j];
+#pragma unroll
+        for (int t = 0; t < QR_MAXK - 1; ++t)
+          if (j + 1 + t < k) Q[i + j + 1 + t] -= c[t] * q;
+      }
+      if (writer) {
+        for (int l = 0; l < j; ++l) R[j * k + l] = 0.;
+        R[j * k + j] = keep ? n1 : 0.;
+#pragma unroll
+        for (int t = 0; t < QR_MAXK - 1; ++t)
+          if (j + 1 + t < k) R[j * k + j + 1 + t] = c[t];
+      }
+    }
   }
 }
 
@@ -285,6 +376,37 @@ int nh_segment_dot(int64_t nseg, const int64_t *ptr_dev, const int32_t *ia_dev, 
     NH_SEGDOT(32)
   }
 #undef NH_SEGDOT
+  NH_LAUNCH_CHECK();
+  return NH_OK;
+}
+
+int nh_aggregate_qr(int64_t nagg, const int64_t *mptr_dev, const int32_t *midx_dev, int64_t nmembers, int k, int64_t n, const double *B_dev, double *Q_dev,
+                    double *Rc_dev, void *stream) {
+  NH_REQUIRE(nagg >= 0 && nmembers >= 0 && n >= 0, "nh_aggregate_qr: negative size");
+  NH_REQUIRE(k >= 1 && k <= QR_MAXK, "nh_aggregate_qr: k must be between 1 and %d (got %d)", QR_MAXK, k);
+  NH_REQUIRE(nmembers <= n, "nh_aggregate_qr: %lld members of %lld rows: a row is in at most one aggregate", (long long)nmembers, (long long)n);
+  NH_REQUIRE(!nagg || (mptr_dev && Rc_dev), "nh_aggregate_qr: NULL aggregate pointers or coarse vectors");
+  NH_REQUIRE(!nmembers || midx_dev, "nh_aggregate_qr: NULL member list");
+  NH_REQUIRE(!n || (B_dev && Q_dev && B_dev != Q_dev), "nh_aggregate_qr: NULL vectors, or the result is the argument");
+  hipStream_t s = nh_stream(stream);
+  if (n) NH_CHECK_HIP(hipMemsetAsync(Q_dev, 0, sizeof(double) * (size_t)n * (size_t)k, s));  // (rows in no aggregate)
+  if (!nagg) return NH_OK;
+  NH_CHECK_HIP(hipMemsetAsync(Rc_dev, 0, sizeof(double) * (size_t)nagg * (size_t)(k * k), s));  // (the first Gram-Schmidt coefficient is added to, not stored)
+  const i64 *mptr = (const i64 *)mptr_dev;
+#define NH_AGGQR(LL)                                                                                                                  \
+  case LL:                                                                                                                            \
+    hipLaunchKernelGGL(k_aggregate_qr<LL>, dim3(spmv_grid(nagg, LL)), dim3(WG), 0, s, (i64)nagg, mptr, midx_dev, k, B_dev, Q_dev, Rc_dev); \
+    break;
+  switch (nh_csr_lanes(nagg, nmembers)) {
+    NH_AGGQR(1)
+    NH_AGGQR(2)
+    NH_AGGQR(4)
+    NH_AGGQR(8)
+    NH_AGGQR(16)
+    default:
+    NH_AGGQR(32)
+  }
+#undef NH_AGGQR
   NH_LAUNCH_CHECK();
   return NH_OK;
 }

@@ -952,6 +952,24 @@ def segment_dot(plan, a, b=None, out=None):
     return out
 
 
+def aggregate_qr(mptr, midx, k, B):
+    '''(Q, Rc): the thin QR of the near-nullspace `B` [n x k] on the rows of every aggregate (nh_aggregate_qr).  Aggregate a has the rows
+    midx[mptr[a] : mptr[a + 1]] (int64 pointers, int32 rows, every row in at most one aggregate); Q [n x k] is 0 on rows in none, Rc [nagg k x k] holds the
+    triangles, the near-nullspace of the next level.  The member list is checked against n here (one look at the device): the kernel writes where it points.'''
+    n, nagg, nmem = B.shape[0], mptr.numel() - 1, midx.numel()
+    if B.dim() != 2 or B.shape[1] != k or not B.is_contiguous() or str(B.dtype) != 'torch.float64':
+        raise ValueError(f'aggregate_qr: B must be a contiguous float64 tensor of shape (n, {k}), got {tuple(B.shape)} {B.dtype}')
+    if str(mptr.dtype) != 'torch.int64' or str(midx.dtype) != 'torch.int32' or nagg < 0:
+        raise ValueError('aggregate_qr: mptr must be int64 [nagg + 1] and midx int32')
+    if nagg and not (int(mptr[0]) == 0 and int(mptr[-1]) == nmem and bool((mptr[1:] >= mptr[:-1]).all())):
+        raise ValueError('aggregate_qr: mptr must rise from 0 to the number of members')
+    if nmem and not (0 <= int(midx.min()) and int(midx.max()) < n):
+        raise ValueError(f'aggregate_qr: member rows must lie in 0 .. {n - 1}')
+    Q, Rc = device.empty(n * k, 'float64').reshape(n, k), device.empty(nagg * k * k, 'float64').reshape(nagg * k, k)
+    _lib.call('nh_aggregate_qr', nagg, device.ptr(mptr), device.ptr(midx), nmem, int(k), n, device.ptr(B), device.ptr(Q), device.ptr(Rc), device.stream())
+    return Q, Rc
+
+
 def csr_jacobi(values, rowptr, colidx, ncols, x, w, b, *, y=None, rowmask=None, col32=None, lanes=0):
     '''y = x + w (b - A x) on the rows the mask keeps, 0 elsewhere, in one launch (nh_csr_jacobi)'''
     if y is None:

@@ -192,7 +192,7 @@ class HipMatrix:
         self.cg_iterations = None
         self.iterations = None
         self._col32 = None
-        self._amg = None  # (free mask, coarse, levels) of the last 'amg' setup: the symbolic phase, reused while pattern and mask stay
+        self._amg = None  # (free mask, coarse, k, levels) of the last 'amg' setup: the symbolic phase, reused while pattern and mask stay
 
     @property
     def size(self):
@@ -348,8 +348,11 @@ class HipMatrix:
         An iterative solve has no "machine precision" mode: atol = rtol = 0 is an error, not a request for it.  `precon`: 'diag' (Jacobi), None, or -- for this
         solver alone -- 'amg': a smoothed-aggregation multigrid V-cycle (the `amg` module has the algorithm), `preconargs=dict(coarse=256, sweeps=1)`: the
         coarsest level has at most `coarse` (1 .. 1024) dofs and is solved densely, its matrix the only thing that visits the host; `sweeps` Jacobi sweeps before
-        and after each coarse correction.  Its symbolic phase runs once per pattern, mask and `coarse` and is handed on by `_with_values`.  The near-nullspace
-        is the constant: a vector problem such as elasticity gets a valid preconditioner, not an optimal one.
+        and after each coarse correction.  The near-nullspace is the constant unless `preconargs` has `nullspace=B`: a float64 host array or device tensor of
+        shape (n, k), or (n,) for k = 1, with 1 <= k <= 6 finite vectors that the smoother reduces slowly -- for elasticity the rigid-body modes
+        (`amg.rigid_body_modes(coords)`), without which a vector problem gets a valid preconditioner, not an optimal one.  Rows of constrained dofs are ignored;
+        a host array crosses PCIe once per solve, as n k doubles.  The symbolic phase runs once per pattern, mask, `coarse` and k and is handed on by
+        `_with_values`.
         `maxiter` defaults to the number of free dofs; `check`: iterations enqueued between two looks at the device's residual norm and breakdown flag (one
         16-byte copy).  Raises ToleranceNotReached(best) when the bound is not met, MatrixError when the matrix turns out not to be positive definite.
 
@@ -391,7 +394,7 @@ class HipMatrix:
             raise MatrixError(f"solver {solver!r} needs a tolerance: pass atol or rtol (an iterative solve has no machine-precision mode)")
         if precon == 'amg' and solver == 'cg':
             from . import amg
-            preconargs = amg.check_args(preconargs)
+            preconargs = amg.check_args(preconargs, ncols)
         elif precon not in ('diag', None):
             raise MatrixError(f"invalid preconditioner {precon!r} for HipMatrix solver {solver!r}: 'diag' or None" + (", or 'amg'" if solver == 'cg' else ''))
         elif preconargs is not None:
@@ -431,14 +434,17 @@ class HipMatrix:
             dinv = (1. / diag).masked_fill(~keep | (diag == 0), 0.)  # (constrained rows: any finite number, their residual is zero)
         return mask, x, b, dinv
 
-    def _amg_hierarchy(self, free, mask, coarse, sweeps):
-        '''the hierarchy of an 'amg' preconditioner (amg.Hierarchy): the symbolic phase is taken from the cache if it was made for this mask and this `coarse`,
-        the numeric phase runs on the values of this matrix'''
-        from . import amg
+    def _amg_hierarchy(self, free, mask, coarse, sweeps, nullspace=None):
+        '''the hierarchy of an 'amg' preconditioner (amg.Hierarchy): the symbolic phase is taken from the cache if it was made for this mask, this `coarse` and
+        this number of near-nullspace vectors, the numeric phase runs on the values of this matrix'''
+        from . import amg, device
         _, rowptr, colidx = self.triplet()
-        if self._amg is None or self._amg[1] != coarse or not numpy.array_equal(self._amg[0], free):
-            self._amg = free.copy(), coarse, amg.symbolic(rowptr, colidx, None if mask is None else mask != 0, coarse)
-        return amg.Hierarchy(self._amg[2], self.triplet()[0], sweeps)
+        k = None if nullspace is None else nullspace.shape[1]
+        if self._amg is None or self._amg[1] != coarse or self._amg[2] != k or not numpy.array_equal(self._amg[0], free):
+            self._amg = free.copy(), coarse, k, amg.symbolic(rowptr, colidx, None if mask is None else mask != 0, coarse, k)
+        if nullspace is not None:  # PCIe: a host array goes up once, n k doubles
+            nullspace = nullspace.contiguous() if _is_tensor(nullspace) else device.to_dev(nullspace, 'float64')
+        return amg.Hierarchy(self._amg[3], self.triplet()[0], sweeps, nullspace)
 
     def _cg(self, rhs, free, lhs, atol, rtol, precon, maxiter, check, on_device, preconargs=None):
         from . import device, kernels

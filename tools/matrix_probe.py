@@ -16,7 +16,8 @@
     fraction of 8 TB/s, and steps, wall time and true residual of a Jacobi-GMRES solve under the conditions of the BiCGStab solve,
   * for the smoothed-aggregation AMG preconditioner (precon='amg'): the time of the symbolic and of the numeric phase of its setup, level sizes and operator
     complexity, one cycle against one masked product, and iterations, wall time and true residual of an AMG-CG solve (with the symbolic phase, and with it
-    cached) beside the Jacobi-CG solve of the same system in the same process.
+    cached) beside the Jacobi-CG solve of the same system in the same process; for the vector matrices (elasticity96, p2vector32) all of that once more with
+    the rigid-body modes as the near-nullspace (preconargs=dict(nullspace=amg.rigid_body_modes(coords))).
 
 Usage: python tools/matrix_probe.py [--matrices poisson128,elasticity96,bilinear2048,bilinear1024,p2vector32] [--scale 1.0] [--sections spmv,cg,bicgstab,fgmres,amg] [--out FILE]
 (--scale shrinks every mesh for a quick look; --sections leaves parts out).  Not run by any test.'''
@@ -147,7 +148,7 @@ def probe(name, args):
     if 'fgmres' in args.sections:
         info['fgmres'] = probe_fgmres(A, free, mask, rhs_dev, res0, args)
     if 'amg' in args.sections:
-        info['amg'] = probe_amg(A, free, mask, rhs_dev, res0, args)
+        info['amg'] = probe_amg(A, free, mask, rhs_dev, res0, info, args)
     return info
 
 
@@ -221,9 +222,16 @@ def probe_cg(A, free, mask, rhs_dev, res0, info, args):
     info['solve']['true_relative_residual'] = float(A.spmv(sol, alpha=-1., beta=1., b=rhs_dev, rowmask=mask).norm() / res0.norm())
 
 
-def probe_amg(A, free, mask, rhs_dev, res0, args):
+def nodes_of(info):
+    '''the coordinates of the nodes of `build`'s mesh, in the order of its dofs'''
+    grids = [numpy.linspace(0, 1, info['degree'] * m + 1) for m in info['shape']]
+    return numpy.stack(numpy.meshgrid(*grids, indexing='ij'), -1).reshape(-1, len(grids))
+
+
+def probe_amg(A, free, mask, rhs_dev, res0, info, args):
     '''precon='amg': the symbolic and the numeric phase of the setup (wall clock, synchronised; the numeric one a first and a second time), one cycle
-    against one masked product, and AMG-CG and Jacobi-CG solves of the same system in the same process'''
+    against one masked product, and AMG-CG and Jacobi-CG solves of the same system in the same process; for a vector matrix the setup and the solve once
+    more with the rigid-body modes as the near-nullspace (on the device beforehand: the solve times hold no upload)'''
     import torch
     from nutils_amd import amg, device, kernels, matrix
     values, rowptr, colidx = A.triplet()
@@ -254,20 +262,46 @@ def probe_amg(A, free, mask, rhs_dev, res0, args):
     out['masked_spmv'] = stats(t_mv)
     out['cycle_over_product'] = out['cycle']['us'] / out['masked_spmv']['us']
     out['launches_per_cycle'] = 5 * (len(levels) - 1) + 1
-    def solve(precon):
+    del h, levels
+    preconargs = {'amg': None, 'diag': None}
+    if info['components'] > 1:
+        B = device.to_dev(amg.rigid_body_modes(nodes_of(info)), 'float64')
+        rbm = out['rigid_body_modes'] = dict(k=B.shape[1])
         try:
-            return A.solve(rhs_dev, constrain=~free, rtol=1e-8, maxiter=args.maxiter, precon=precon), True
+            levels, rbm['symbolic_ms'] = clocked(lambda: amg.symbolic(rowptr, colidx, mask != 0, 256, B.shape[1]))
+            h, rbm['numeric_first_ms'] = clocked(lambda: amg.Hierarchy(levels, values, 1, B))
+            h, rbm['numeric_ms'] = clocked(lambda: amg.Hierarchy(levels, values, 1, B))
+            rbm['levels'] = [lv.nfree for lv in levels]
+            rbm['kinds'] = [lv.kind for lv in levels]
+            rbm['operator_complexity'] = sum(lv.colidx.numel() for lv in levels) / nnzs[0]
+            rbm['dropped_columns'] = [int((d.dinv == 0).sum()) for lv, d in zip(levels[1:], h.data[1:])]
+            t_cycle, = windows([lambda: h.apply(r, z)], args.window)
+            rbm['cycle'] = stats(t_cycle)
+            rbm['cycle_over_product'] = rbm['cycle']['us'] / out['masked_spmv']['us']
+            del h, levels
+            preconargs['amg_rbm'] = dict(nullspace=B)
+        except (matrix.MatrixError, RuntimeError) as e:  # (as above: recorded, not hidden)
+            rbm['error'] = f'{type(e).__name__}: {e}'
+
+    def solve(name):
+        try:
+            return A.solve(rhs_dev, constrain=~free, rtol=1e-8, maxiter=args.maxiter, precon=name.split('_')[0], preconargs=preconargs[name]), True
         except matrix.ToleranceNotReached as e:
             return e.best, False
 
-    A._amg = None
-    runs = {precon: [clocked(lambda: solve(precon))] for precon in ('amg', 'diag')}  # the first 'amg' solve runs the symbolic phase, the later ones find it cached
+    runs, cached = {}, {}
+    for name in preconargs:  # the first solve of an 'amg' kind runs its symbolic phase; the matrix caches one, so each kind is handed its own back below
+        A._amg = None
+        runs[name] = [clocked(lambda: solve(name))]
+        cached[name] = A._amg
     for _ in range(3):  # (alternating)
         for precon in runs:
+            A._amg = cached[precon]
             runs[precon].append(clocked(lambda: solve(precon)))
     for precon, timed in runs.items():
         (sol, converged), first = timed[0]
         res = dict(converged=converged, first_ms=first, wall_ms=float(numpy.median([ms for _, ms in timed[1:]])), spread=(max(ms for _, ms in timed[1:]) - min(ms for _, ms in timed[1:])))
+        A._amg = cached[precon]
         solve(precon)
         res['iterations'] = A.iterations
         res['true_relative_residual'] = float(A.spmv(sol, alpha=-1., beta=1., b=rhs_dev, rowmask=mask).norm() / res0.norm())
