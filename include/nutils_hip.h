@@ -774,9 +774,23 @@ int nh_gmres_update(int64_t n, int restart, const double *dinv_dev, const double
  * (q_j = 0 and R[j][j] = 0 exactly, R[l][j] kept), otherwise q_j /= n1 and R[j][j] = n1.  Lanes per aggregate follow from the mean size by the rule of
  * nh_csr_lanes.  Q_dev must not be B_dev.
  * nh_csr_jacobi: y = x + w (b - A x) on the rows the mask keeps, 0 on the others, in one launch; y must not be x.
+ * nh_csr_chebyshev: one step of the Chebyshev smoother in one launch, on the mapping of nh_csr_jacobi: dout = c1 d + c2 dinv (b - A x), y = x + dout on the rows
+ * the mask keeps, +0 in both on the others; coef_dev: the two doubles (c1, c2) on the device.  d_dev NULL is the first step of a polynomial, dout = c2 dinv
+ * (b - A x): neither d nor c1 is read (there is no 0 * d).  y must not be x; dout may be d.
+ * nh_csr_lanczos: `steps` >= 1 steps of the Lanczos recurrence on S A_f S, S = diag(s_dev) (s = sqrt(1 / diag), 0 where a row takes no part), enqueued: three
+ * launches a step and two at the start, nothing read back.  q_0 = u0 / |u0| with u0 = u_dev on the rows the mask keeps and where s != 0, 0 elsewhere; step j:
+ * w = s (mask(A (s q_j))) with the partials of q_j . w; alpha_j from them (summed by every workgroup in the same order), w -= alpha_j q_j + beta_j q_(j-1)
+ * (beta_0 = 0: no q_(-1) is read) with the partials of w . w; beta_(j+1) = |w|, q_(j+1) = w / beta_(j+1) and s q_(j+1) for the next product.  out_dev: 2 steps
+ * + 1 doubles, zero-filled first: out[2 j] = alpha_j, out[2 j + 1] = beta_(j+1), out[2 steps] = the number of steps taken.  A beta_(j+1) that is 0 or not
+ * finite ends the recurrence with j + 1 steps taken (so does a start vector without a finite positive norm, with none); the launches after it idle.
+ * work_dev: 4 n + NH_LANCZOS_CELLS doubles, the caller's, of no meaning afterwards.  n = 0: out is zero-filled, no launch.
  * nh_amg is a hierarchy made of level descriptions; like nh_csr it holds views and owns no device memory, and every vector of a description is the caller's
  * to allocate and to keep.  Level l < nlevels - 1 has kind NH_AMG_COARSEN: A (its matrix), rowmask_dev (level 0 only; NULL: all rows), w_dev = omega / diag
  * (0 on masked rows), P [n x n_c] and R = P^T [n_c x n] as CSR views of their own, sweeps >= 1, t_dev and r_dev: n doubles each; for l > 0 also b_dev and x_dev.
+ * smoother = NH_AMG_CHEBYSHEV (NH_AMG_JACOBI = 0: a zero-filled tail is the Jacobi level above) makes the level's smoother the Chebyshev polynomial of
+ * `degree` >= 1 steps: w_dev = 1 / diag (0 on masked rows, no omega), coef_dev: 2 degree doubles, (c1, c2) of step 0, 1, .. (c1 of step 0 is never read),
+ * d_dev: n doubles, `sweeps` is not read.  Before the coarse correction x = d = c2 w b, then steps 1 .. degree - 1 of nh_csr_chebyshev; after it steps
+ * 0 .. degree - 1, the first without d: the launches of a Jacobi level with sweeps = degree.
  * The last level is NH_AMG_DENSE -- Ainv_dev [ndense x ndense] row-major, ndense <= 1024; idx_dev int32 [ndense] lists the rows it acts on when ndense is
  * less than the rows of A (a masked level 0), whose other rows get 0 -- or NH_AMG_DIAGONAL, z = w b with w_dev = 1 / diag.
  * nh_amg_apply enqueues z = M r, one V(sweeps, sweeps) cycle from level 0, and returns: the first sweep x = w b, further ones x += w (b - A x), then
@@ -788,6 +802,8 @@ int nh_gmres_update(int64_t n, int restart, const double *dinv_dev, const double
  * first r . z, r . r from a given r, and clears flag and bound. */
 typedef struct nh_amg nh_amg;
 enum { NH_AMG_COARSEN = 0, NH_AMG_DENSE = 1, NH_AMG_DIAGONAL = 2 };
+enum { NH_AMG_JACOBI = 0, NH_AMG_CHEBYSHEV = 1 };
+enum { NH_LANCZOS_CELLS = 4096 };
 typedef struct {
   nh_csr A;
   const unsigned char *rowmask_dev;
@@ -798,6 +814,9 @@ typedef struct {
   int64_t ndense;
   const double *Ainv_dev;
   const int32_t *idx_dev;
+  int smoother, degree;
+  const double *coef_dev;
+  double *d_dev;
 } nh_amg_level;
 
 int nh_segment_dot(int64_t nseg, const int64_t *ptr_dev, const int32_t *ia_dev, const int32_t *ib_dev, const double *a_dev, const double *b_dev, int64_t nprod,
@@ -805,6 +824,10 @@ int nh_segment_dot(int64_t nseg, const int64_t *ptr_dev, const int32_t *ia_dev, 
 int nh_aggregate_qr(int64_t nagg, const int64_t *mptr_dev, const int32_t *midx_dev, int64_t nmembers, int k, int64_t n, const double *B_dev, double *Q_dev,
                     double *Rc_dev, void *stream);
 int nh_csr_jacobi(const nh_csr *A, const double *x_dev, const double *w_dev, const double *b_dev, const unsigned char *rowmask_dev, double *y_dev, void *stream);
+int nh_csr_chebyshev(const nh_csr *A, const double *x_dev, const double *d_dev, const double *dinv_dev, const double *b_dev, const double *coef_dev,
+                     const unsigned char *rowmask_dev, double *y_dev, double *dout_dev, void *stream);
+int nh_csr_lanczos(const nh_csr *A, const double *s_dev, const unsigned char *rowmask_dev, const double *u_dev, int steps, double *work_dev, double *out_dev,
+                   void *stream);
 int nh_amg_create(const nh_amg_level *levels, int nlevels, nh_amg **out);
 int nh_amg_free(nh_amg *amg);
 int nh_amg_apply(const nh_amg *amg, const double *r_dev, double *z_dev, void *stream);

@@ -129,10 +129,13 @@ class Csr(ctypes.Structure):
 
 class AmgLevel(ctypes.Structure):
     _fields_ = [('A', Csr), ('rowmask_dev', vp), ('w_dev', vp), ('P', Csr), ('R', Csr), ('b_dev', vp), ('x_dev', vp), ('t_dev', vp), ('r_dev', vp),
-                ('kind', ctypes.c_int), ('sweeps', ctypes.c_int), ('ndense', c_i64), ('Ainv_dev', vp), ('idx_dev', vp)]
+                ('kind', ctypes.c_int), ('sweeps', ctypes.c_int), ('ndense', c_i64), ('Ainv_dev', vp), ('idx_dev', vp),
+                ('smoother', ctypes.c_int), ('degree', ctypes.c_int), ('coef_dev', vp), ('d_dev', vp)]
 
 
 AMG_KINDS = {'coarsen': 0, 'dense': 1, 'diagonal': 2}
+AMG_SMOOTHERS = {'jacobi': 0, 'chebyshev': 1}
+LANCZOS_CELLS = 4096  # NH_LANCZOS_CELLS: what the work array of nh_csr_lanczos holds besides its four vectors
 
 GEOM_ISO = 1
 GEOM_BOX = 2
@@ -220,6 +223,8 @@ SIGNATURES = {
     'nh_segment_dot': (ctypes.c_int, [c_i64, vp, vp, vp, vp, vp, c_i64, vp, vp]),
     'nh_aggregate_qr': (ctypes.c_int, [c_i64, vp, vp, c_i64, ctypes.c_int, c_i64, vp, vp, vp, vp]),
     'nh_csr_jacobi': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, vp, vp, vp, vp]),
+    'nh_csr_chebyshev': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    'nh_csr_lanczos': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, vp, ctypes.c_int, vp, vp, vp]),
     'nh_amg_create': (ctypes.c_int, [ctypes.POINTER(AmgLevel), ctypes.c_int, ctypes.POINTER(vp)]),
     'nh_amg_free': (ctypes.c_int, [vp]),
     'nh_amg_apply': (ctypes.c_int, [vp, vp, vp, vp]),

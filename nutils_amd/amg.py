@@ -4,8 +4,9 @@ Two phases.  ``symbolic`` reads the pattern and the constraint mask only and is 
 live (on the device in a solve, on CPU tensors in the tests): the aggregates, the CSR patterns of the prolongator P, the restriction R = P^T and the
 coarse matrix A_c = R A P, and for each of the products A T, A P and R (A P) an expand-sort-compress plan -- the products of the sparse product listed,
 sorted stably by output entry and cut into segments.  ``numeric`` reads values, on the device: every sparse product is one nh_segment_dot over its
-plan, the step from A T to P and to the smoother's weights is elementwise, and the only thing that visits the host is the coarsest matrix (at most
-``coarse``^2 doubles over PCIe), whose pseudo-inverse is computed there by numpy and applied on the device as a dense product.
+plan, the step from A T to P and to the smoother's weights is elementwise, and the only matrix that visits the host is the coarsest (at most
+``coarse``^2 doubles over PCIe), whose pseudo-inverse is computed there by numpy and applied on the device as a dense product.  With the Chebyshev
+smoother a level also sends the host the coefficients of its Lanczos recurrence (2 eigsteps + 1 doubles) and its rho, and gets 2 degree doubles back.
 
 The algorithm, level by level (A_f: the matrix on the free rows and columns; never formed on the finest level, where the row mask and zero rows of P
 do it; coarse levels have no mask).  The pattern must be structurally symmetric.
@@ -24,6 +25,15 @@ termination  a level with at most ``coarse`` free dofs is solved densely (numpy.
              solved by z = dinv b; any other level is coarsened.
 cycle        V(sweeps, sweeps): x = omega dinv b, further sweeps x += omega dinv (b - A x), r = b - A x, x += P cycle(R r), `sweeps` sweeps more.  Equal
              pre- and post-smoothing with omega < 2 / rho keeps the cycle symmetric positive definite, which CG needs.
+chebyshev    ``smoother='chebyshev'`` (``degree=2, eigsteps=10, eigratio=10.``) replaces the Jacobi sweeps of every coarsened level by a Chebyshev polynomial in
+             D^-1 A_f; P and the hierarchy stay as they are.  Estimate: `eigsteps` Lanczos steps on S A_f S, S = sqrt(dinv), from q_0 = u / |u|, u = the top 31
+             bits of the hash of ``keys`` scaled to [-1, 1) (``start_vector``), 0 on masked rows and where dinv = 0 (nh_csr_lanczos; a vanishing or
+             non-finite beta ends it early); theta = the largest eigenvalue of the tridiagonal matrix, by numpy on the host.  Bounds: ub = min(1.1 theta, rho)
+             (theta approaches the largest eigenvalue from below, rho is a true bound), lb = ub / eigratio.  Smoother: with tc = (ub + lb) / 2,
+             delta = (ub - lb) / 2, rho_0 = delta / tc, rho_k = 1 / (2 tc / delta - rho_(k-1)): d = dinv (b - A x) / tc, x += d, then
+             d = rho_k rho_(k-1) d + (2 rho_k / delta) dinv (b - A x), x += d for k = 1 .. degree - 1.  Before the coarse correction it starts from x = 0 (no
+             product in the first step), after it the same `degree` steps run on the corrected x: equal polynomials keep the cycle symmetric, ub at or
+             above the largest eigenvalue keeps it positive definite.  A cycle of degree d costs what a Jacobi cycle with sweeps = d costs.
 
 Without further arguments the constant is the only near-nullspace vector, which is right for scalar problems; elasticity then gets a valid preconditioner,
 not an optimal one.  A vector problem hands its near-nullspace B [n x k], k <= 6, to the setup (``preconargs=dict(nullspace=B)``; for elasticity the
@@ -288,6 +298,64 @@ def check_args(preconargs, n=None):
     return int(coarse), int(sweeps), B
 
 
+SMOOTHER_KEYS = 'smoother', 'degree', 'eigsteps', 'eigratio'
+
+
+def split_smoother(preconargs):
+    '''(rest, smoother): the smoother keys of `preconargs` taken out and validated, the others left for `check_args`.  smoother: None for 'jacobi' (the
+    default), or dict(degree=2, eigsteps=10, eigratio=10.) for 'chebyshev' with the values given filled in.'''
+    from .matrix import MatrixError
+    rest = dict(preconargs or {})
+    given = {key: rest.pop(key) for key in SMOOTHER_KEYS if key in rest}
+    kind = given.pop('smoother', 'jacobi')
+    if not (isinstance(kind, str) and kind in ('jacobi', 'chebyshev')):
+        raise MatrixError(f"amg: smoother must be 'jacobi' or 'chebyshev', got {kind!r}")
+    if kind == 'jacobi':
+        if given:
+            raise MatrixError(f"amg: {sorted(given)} are arguments of smoother='chebyshev'; the 'jacobi' smoother takes 'sweeps'")
+        return rest, None
+    isint = lambda v: isinstance(v, (int, numpy.integer)) and not isinstance(v, bool)
+    degree, eigsteps, eigratio = given.get('degree', 2), given.get('eigsteps', 10), given.get('eigratio', 10.)
+    if not (isint(degree) and 1 <= degree <= 8):
+        raise MatrixError(f'amg: degree must be an integer between 1 and 8, got {degree!r}')
+    if not (isint(eigsteps) and 1 <= eigsteps <= 64):
+        raise MatrixError(f'amg: eigsteps must be an integer between 1 and 64, got {eigsteps!r}')
+    if not (isinstance(eigratio, (int, float, numpy.integer, numpy.floating)) and not isinstance(eigratio, bool) and numpy.isfinite(eigratio) and eigratio > 1):
+        raise MatrixError(f'amg: eigratio must be a finite number greater than 1, got {eigratio!r}')
+    if rest.get('sweeps', 1) != 1 or isinstance(rest.get('sweeps', 1), bool):
+        raise MatrixError("amg: sweeps counts the sweeps of the 'jacobi' smoother; with smoother='chebyshev' it is `degree` that says how much smoothing is done")
+    return rest, dict(degree=int(degree), eigsteps=int(eigsteps), eigratio=float(eigratio))
+
+
+def start_vector(n, device=None):
+    '''the start vector of the Lanczos recurrence: the top 31 bits of the hash of `keys`, as a number in [-1, 1)'''
+    return (keys(n, device) >> 32).to(_torch().float64) * 2. ** -30 - 1.
+
+
+def chebyshev_coefficients(ub, lb, degree):
+    '''the pairs (c1, c2) of the steps d = c1 d + c2 dinv (b - A x), x += d of the Chebyshev polynomial of the interval [lb, ub], as a flat host array of
+    2 degree numbers: theta = (ub + lb) / 2, delta = (ub - lb) / 2, rho_0 = delta / theta, rho_k = 1 / (2 theta / delta - rho_(k-1)); step 0 has (0, 1 / theta),
+    step k (rho_k rho_(k-1), 2 rho_k / delta)'''
+    theta, delta = (ub + lb) / 2., (ub - lb) / 2.
+    coef, rho = [0., 1. / theta], delta / theta
+    for _ in range(1, degree):
+        new = 1. / (2. * theta / delta - rho)
+        coef += [new * rho, 2. * new / delta]
+        rho = new
+    return numpy.array(coef)
+
+
+def lanczos_theta(out):
+    '''(theta, steps): the largest eigenvalue of the tridiagonal matrix of the alpha_j, beta_(j+1) that nh_csr_lanczos left in `out` (a host array), and the number
+    of steps it took; theta is nan when there is none'''
+    steps = int(out[-1])
+    if not steps:
+        return numpy.nan, 0
+    alpha, beta = out[0:2 * steps:2], out[1:2 * steps - 1:2]
+    T = numpy.diag(alpha) + numpy.diag(beta, 1) + numpy.diag(beta, -1)
+    return (float(numpy.linalg.eigvalsh(T)[-1]) if numpy.isfinite(T).all() else numpy.nan), steps
+
+
 def rigid_body_modes(coords):
     '''The near-nullspace of linear elasticity from the node coordinates `coords` [nnodes x d], d = 2 or 3: a host array [nnodes d x d (d + 1) / 2] whose
     columns are the d translations and then the rotations ((-y, x) in 2-D; about the x, y and z axis in 3-D), in the dof layout of a vector field
@@ -313,9 +381,11 @@ class Hierarchy:
     cycle.  `levels`: of `symbolic`, on device tensors.  Per level `self.data[l]` keeps what the cycle reads: values, dinv, and for a coarsened level rho,
     omega (0-dim device tensors), w = omega dinv, pvalues, rvalues; for a dense level ainv.  `nullspace`: the near-nullspace of level 0, a float64 device
     tensor [n x k], for levels of ``symbolic(..., nullspace=k)``; a coarsened level then keeps its own as B, the values of T as q [n x k], and hands the
-    triangles of the aggregates' QR on as the B of the next.'''
+    triangles of the aggregates' QR on as the B of the next.  `smoother`: None (Jacobi) or the dict of `split_smoother`; a coarsened level then also keeps the
+    Lanczos estimate theta of the largest eigenvalue of D^-1 A_f with the steps it took (eigsteps), ub, lb (host numbers), the coefficients of its polynomial
+    (coef: 2 degree doubles on the device) and the vector d of the recurrence.  The estimate costs one look at the device per level: 2 eigsteps + 1 doubles.'''
 
-    def __init__(self, levels, values, sweeps=1, nullspace=None):
+    def __init__(self, levels, values, sweeps=1, nullspace=None, smoother=None):
         from . import device, kernels
         from .matrix import MatrixError, spmv_lanes
         torch = _torch()
@@ -364,7 +434,19 @@ class Hierarchy:
             d.rvalues = d.pvalues[lv.rperm]
             d.apvalues = kernels.segment_dot(lv.ap, values, d.pvalues)
             d.t, d.r = device.empty(lv.n, 'float64'), device.empty(lv.n, 'float64')
-            desc.update(kind='coarsen', w=d.w, t=d.t, r=d.r, P=(d.pvalues, lv.prowptr, lv.pcol, lv.nc, lv.pcol32, 0), R=(d.rvalues, lv.rrowptr, lv.rcol, lv.n, lv.rcol32, 0))
+            if smoother is not None:
+                # PCIe: the alpha and beta of the recurrence and its step count visit the host, and so does rho, one number
+                out = kernels.csr_lanczos(values, lv.rowptr, lv.colidx, lv.n, d.dinv.sqrt(), start_vector(lv.n, values.device), smoother['eigsteps'], rowmask=lv.mask,
+                                          col32=lv.col32, lanes=lanes)
+                d.theta, d.eigsteps = lanczos_theta(device.to_host(out))
+                if not (d.theta > 0 and numpy.isfinite(d.theta)):
+                    raise MatrixError('amg: matrix is not positive definite')
+                d.ub = min(1.1 * d.theta, float(d.rho))  # (theta comes from below, rho is a true bound)
+                d.lb = d.ub / smoother['eigratio']
+                d.coef = device.to_dev(chebyshev_coefficients(d.ub, d.lb, smoother['degree']), 'float64')
+                d.d = device.empty(lv.n, 'float64')
+                desc.update(smoother='chebyshev', degree=smoother['degree'], coef=d.coef, d=d.d)
+            desc.update(kind='coarsen', w=d.w if smoother is None else d.dinv, t=d.t, r=d.r, P=(d.pvalues, lv.prowptr, lv.pcol, lv.nc, lv.pcol32, 0), R=(d.rvalues, lv.rrowptr, lv.rcol, lv.n, lv.rcol32, 0))
             values = kernels.segment_dot(lv.rap, d.rvalues, d.apvalues)
         self.handle = kernels.Amg(descriptions)
 

@@ -11,6 +11,10 @@
 //     tentative prolongator, the triangles R are the near-nullspace of the next level.  L lanes own an aggregate (chosen from the mean size as above), rows
 //     strided over them, norms and dots folded with __shfl_xor.  Once per hierarchy build.
 //   * k_jacobi<L, Idx>: y = x + w (b - A x) on the rows the mask keeps, 0 elsewhere, in one launch (k_csr_spmv with another epilogue; y != x).
+//   * k_chebyshev<L, Idx, FIRST>: a step of the Chebyshev smoother, dout = c1 d + c2 dinv (b - A x), y = x + dout, on the mapping of k_jacobi; k_chebyshev_start
+//     is the step from x = 0.  The coefficient pairs of a level's polynomial are a small device array the host computed from its eigenvalue bounds.
+//   * k_lanczos_*: the Lanczos recurrence on S A_f S that estimates the largest eigenvalue of D^-1 A_f for those bounds: three launches a step (product with the
+//     partials of q . w; update with the partials of w . w; normalisation, which stores alpha and beta), a pair of status cells that makes later steps idle.
 //   * k_scale: y = w b, the sweep that starts from zero, and the solve of a diagonal terminal level.
 //   * k_dense: z = Ainv b for the coarsest level, one workgroup, a wave per row, lanes over the columns.
 //   * the cycle (amg_cycle) is a host loop over the level descriptions that enqueues those kernels and nh_csr_spmv (residual, restriction,
@@ -176,6 +180,169 @@ __global__ __launch_bounds__(WG) void k_scale(i64 n, const double *__restrict__ 
   for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < n; i += (i64)gridDim.x * WG) y[i] = w[i] * b[i];
 }
 
+// One step of the Chebyshev smoother: dout = c1 d + c2 dinv (b - A x), y = x + dout on the rows the mask keeps, +0 in both elsewhere (k_jacobi with another
+// epilogue; y != x).  coef = (c1, c2) on the device.  FIRST: the first step of a polynomial, which has no d term: neither d nor c1 is read.  d and dout are not
+// restrict: a row reads d[row] before it writes dout[row] and no other row does either, so the update may be in place.
+template <int L, class Idx, bool FIRST>
+__global__ __launch_bounds__(WG) void k_chebyshev(i64 nrows, const i64 *__restrict__ rowptr, const Idx *__restrict__ col, const double *__restrict__ values,
+                                                  const double *__restrict__ x, const double *d, const double *__restrict__ dinv, const double *__restrict__ b,
+                                                  const double *__restrict__ coef, const unsigned char *__restrict__ mask, double *__restrict__ y, double *dout) {
+  constexpr int G = WG / L;
+  const int lane = threadIdx.x & (L - 1);
+  const double c1 = FIRST ? 0. : coef[0], c2 = coef[1];
+  for (i64 base = (i64)blockIdx.x * G; base < nrows; base += (i64)gridDim.x * G) {
+    const i64 row = base + threadIdx.x / L;
+    const bool live = row < nrows;
+    const bool on = live && (!mask || mask[row]);
+    double s = 0;
+    if (on) {
+      const i64 k1 = rowptr[row + 1];
+#pragma unroll 2
+      for (i64 k = rowptr[row] + lane; k < k1; k += L) s += values[k] * x[col[k]];
+    }
+#pragma unroll
+    for (int o = L >> 1; o; o >>= 1) s += __shfl_xor(s, o, L);
+    if (live && lane == 0) {
+      double v = 0., xi = 0.;
+      if (on) {
+        v = c2 * dinv[row] * (b[row] - s);
+        if (!FIRST) v += c1 * d[row];
+        xi = x[row] + v;
+      }
+      dout[row] = v;
+      y[row] = xi;
+    }
+  }
+}
+
+// x = d = c2 w b: step 0 of the polynomial from x = 0, which needs no product
+__global__ __launch_bounds__(WG) void k_chebyshev_start(i64 n, const double *__restrict__ coef, const double *__restrict__ w, const double *__restrict__ b,
+                                                        double *__restrict__ d, double *__restrict__ x) {
+  const double c2 = coef[1];
+  for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < n; i += (i64)gridDim.x * WG) {
+    const double v = c2 * w[i] * b[i];
+    d[i] = v;
+    x[i] = v;
+  }
+}
+
+// The Lanczos recurrence on S A_f S (nh_csr_lanczos).  The cells of its work array: who stopped (two cells, one read and one written per kernel, as in the CG
+// kernels: ST_B is read by the product and the update, which copies it to ST_A; ST_A is read by the normalisation, which writes ST_B), alpha of the step (written
+// by the update, read by the normalisation), beta (written by the normalisation, read by the next update), and the partials of the two dots.
+enum { Z_ST_A = 0, Z_ST_B = 1, Z_ALPHA = 2, Z_BETA = 3, Z_PA = 8, Z_PB = Z_PA + SPMV_MAX_WGS, Z_END = Z_PB + VEC_MAX_WGS };
+static_assert(Z_END <= NH_LANCZOS_CELLS, "the cells of nh_csr_lanczos outgrow what the header promises");
+
+__device__ __forceinline__ bool positive_finite(double v) { return v > 0. && v <= 1.7976931348623157e308; }
+
+// q = u on the rows that take part (mask, s != 0), 0 elsewhere; partials of q . q
+__global__ __launch_bounds__(WG) void k_lanczos_start(i64 n, const double *__restrict__ u, const double *__restrict__ s, const unsigned char *__restrict__ mask,
+                                                      double *__restrict__ q, double *work) {
+  __shared__ double lds[4];
+  double acc = 0;
+  for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < n; i += (i64)gridDim.x * WG) {
+    const double v = (!mask || mask[i]) && s[i] != 0. ? u[i] : 0.;
+    q[i] = v;
+    acc += v * v;
+  }
+  acc = block_sum(acc, lds);
+  if (threadIdx.x == 0) work[Z_PB + blockIdx.x] = acc;
+}
+
+// q_0 = q / |q|, sq = s q_0, the cells; a start vector without a finite positive norm stops the recurrence before its first step
+__global__ __launch_bounds__(WG) void k_lanczos_first(i64 n, int nparts, const double *__restrict__ s, double *__restrict__ q, double *__restrict__ sq, double *work) {
+  __shared__ double lds[4];
+  const double norm = sqrt(partial_sum(work + Z_PB, nparts, lds));
+  const bool stop = !positive_finite(norm);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    work[Z_ST_A] = work[Z_ST_B] = stop ? 1. : 0.;
+    work[Z_ALPHA] = work[Z_BETA] = 0.;
+  }
+  if (stop) return;
+  for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < n; i += (i64)gridDim.x * WG) {
+    const double v = q[i] / norm;
+    q[i] = v;
+    sq[i] = s[i] * v;
+  }
+}
+
+// w = s mask(A sq), partials of q . w (k_csr_spmv with DOT = 1 and another epilogue)
+template <int L, class Idx>
+__global__ __launch_bounds__(WG) void k_lanczos_product(i64 nrows, const i64 *__restrict__ rowptr, const Idx *__restrict__ col, const double *__restrict__ values,
+                                                        const double *__restrict__ sq, const double *__restrict__ s, const double *__restrict__ q,
+                                                        const unsigned char *__restrict__ mask, double *__restrict__ w, double *work) {
+  if (work[Z_ST_B] != 0.) return;
+  constexpr int G = WG / L;
+  const int lane = threadIdx.x & (L - 1);
+  double dot = 0;
+  for (i64 base = (i64)blockIdx.x * G; base < nrows; base += (i64)gridDim.x * G) {
+    const i64 row = base + threadIdx.x / L;
+    const bool live = row < nrows;
+    const bool on = live && (!mask || mask[row]);
+    double t = 0;
+    if (on) {
+      const i64 k1 = rowptr[row + 1];
+#pragma unroll 2
+      for (i64 k = rowptr[row] + lane; k < k1; k += L) t += values[k] * sq[col[k]];
+    }
+#pragma unroll
+    for (int o = L >> 1; o; o >>= 1) t += __shfl_xor(t, o, L);
+    if (live && lane == 0) {
+      const double v = on ? s[row] * t : 0.;
+      w[row] = v;
+      dot += q[row] * v;
+    }
+  }
+  __shared__ double lds[4];
+  dot = block_sum(dot, lds);
+  if (threadIdx.x == 0) work[Z_PA + blockIdx.x] = dot;
+}
+
+// alpha = q . w; w -= alpha q + beta qprev (first: beta = 0 and qprev is not read); partials of w . w
+__global__ __launch_bounds__(WG) void k_lanczos_update(i64 n, int npa, int first, const double *__restrict__ q, const double *__restrict__ qprev, double *__restrict__ w,
+                                                       double *work) {
+  __shared__ double lds[4];
+  const bool stopped = work[Z_ST_B] != 0.;
+  if (blockIdx.x == 0 && threadIdx.x == 0) work[Z_ST_A] = stopped ? 1. : 0.;
+  if (stopped) return;
+  const double alpha = partial_sum(work + Z_PA, npa, lds), beta = work[Z_BETA];
+  if (blockIdx.x == 0 && threadIdx.x == 0) work[Z_ALPHA] = alpha;
+  double acc = 0;
+  for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < n; i += (i64)gridDim.x * WG) {
+    double v = w[i] - alpha * q[i];
+    if (!first) v -= beta * qprev[i];
+    w[i] = v;
+    acc += v * v;
+  }
+  acc = block_sum(acc, lds);
+  if (threadIdx.x == 0) work[Z_PB + blockIdx.x] = acc;
+}
+
+// beta = |w|; alpha_j, beta_(j+1) and the count to `out`; q_(j+1) = w / beta in place, sq = s q_(j+1).  beta = 0 or not finite: the recurrence ends here
+__global__ __launch_bounds__(WG) void k_lanczos_normalize(i64 n, int nparts, int j, int steps, const double *__restrict__ s, double *__restrict__ w, double *__restrict__ sq,
+                                                          double *work, double *__restrict__ out) {
+  __shared__ double lds[4];
+  const bool stopped = work[Z_ST_A] != 0.;
+  if (stopped) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) work[Z_ST_B] = 1.;
+    return;
+  }
+  const double beta = sqrt(partial_sum(work + Z_PB, nparts, lds));
+  const bool stop = !positive_finite(beta);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    out[2 * j] = work[Z_ALPHA];
+    out[2 * j + 1] = beta;
+    out[2 * steps] = j + 1;
+    work[Z_BETA] = beta;
+    work[Z_ST_B] = stop ? 1. : 0.;
+  }
+  if (stop) return;
+  for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < n; i += (i64)gridDim.x * WG) {
+    const double v = w[i] / beta;
+    w[i] = v;
+    sq[i] = s[i] * v;
+  }
+}
+
 // z[idx[i]] = sum_j Ainv[i][j] b[idx[j]], i < m (idx == NULL: the identity); other rows of z are not touched (the caller has zeroed them).  One workgroup: a
 // wave per row, its lanes stride over the columns and are folded in a fixed order.
 __global__ __launch_bounds__(DENSE_WG) void k_dense(int m, const double *__restrict__ Ainv, const double *__restrict__ b, const int32_t *__restrict__ idx,
@@ -318,7 +485,70 @@ int scale(i64 n, const double *w, const double *b, double *y, hipStream_t s) {
   return NH_OK;
 }
 
-// x = M b on level l.  The sweeps alternate between the level's two vectors: there are 2 sweeps - 1 that swap, so the cycle starts in t and ends in x.
+template <class Idx, bool FIRST>
+void launch_chebyshev(int L, const nh_csr &A, const Idx *col, const double *x, const double *d, const double *dinv, const double *b, const double *coef,
+                      const unsigned char *mask, double *y, double *dout, hipStream_t s) {
+#define NH_CHEBYSHEV(LL)                                                                                                                                             \
+  case LL:                                                                                                                                                           \
+    hipLaunchKernelGGL((k_chebyshev<LL, Idx, FIRST>), dim3(spmv_grid(A.nrows, LL)), dim3(WG), 0, s, (i64)A.nrows, (const i64 *)A.rowptr_dev, col, A.values_dev, x, d, dinv, \
+                       b, coef, mask, y, dout);                                                                                                                      \
+    break;
+  switch (L) {
+    NH_CHEBYSHEV(1)
+    NH_CHEBYSHEV(2)
+    NH_CHEBYSHEV(4)
+    NH_CHEBYSHEV(8)
+    NH_CHEBYSHEV(16)
+    NH_CHEBYSHEV(32)
+    default:
+    NH_CHEBYSHEV(64)
+  }
+#undef NH_CHEBYSHEV
+}
+
+// dout = c1 d + c2 dinv (b - A x), y = mask(x + dout); d == NULL: the first step, without d; the caller has checked the view
+int chebyshev(const nh_csr &A, const double *x, const double *d, const double *dinv, const double *b, const double *coef, const unsigned char *mask, double *y,
+              double *dout, hipStream_t s) {
+  if (!A.nrows) return NH_OK;
+  const int L = A.lanes ? A.lanes : nh_csr_lanes(A.nrows, A.nnz);
+  if (A.col32_dev) {
+    if (d)
+      launch_chebyshev<int32_t, false>(L, A, A.col32_dev, x, d, dinv, b, coef, mask, y, dout, s);
+    else
+      launch_chebyshev<int32_t, true>(L, A, A.col32_dev, x, d, dinv, b, coef, mask, y, dout, s);
+  } else {
+    if (d)
+      launch_chebyshev<i64, false>(L, A, (const i64 *)A.colidx_dev, x, d, dinv, b, coef, mask, y, dout, s);
+    else
+      launch_chebyshev<i64, true>(L, A, (const i64 *)A.colidx_dev, x, d, dinv, b, coef, mask, y, dout, s);
+  }
+  NH_LAUNCH_CHECK();
+  return NH_OK;
+}
+
+template <class Idx>
+void launch_lanczos_product(int L, const nh_csr &A, const Idx *col, const double *sq, const double *sc, const double *q, const unsigned char *mask, double *w,
+                            double *work, hipStream_t s) {
+#define NH_LANCZOS(LL)                                                                                                                                              \
+  case LL:                                                                                                                                                          \
+    hipLaunchKernelGGL((k_lanczos_product<LL, Idx>), dim3(spmv_grid(A.nrows, LL)), dim3(WG), 0, s, (i64)A.nrows, (const i64 *)A.rowptr_dev, col, A.values_dev, sq, sc, q, \
+                       mask, w, work);                                                                                                                              \
+    break;
+  switch (L) {
+    NH_LANCZOS(1)
+    NH_LANCZOS(2)
+    NH_LANCZOS(4)
+    NH_LANCZOS(8)
+    NH_LANCZOS(16)
+    NH_LANCZOS(32)
+    default:
+    NH_LANCZOS(64)
+  }
+#undef NH_LANCZOS
+}
+
+// x = M b on level l.  The sweeps alternate between the level's two vectors: there are 2 sweeps - 1 that swap, so the cycle starts in t and ends in x.  A
+// Chebyshev level of degree d takes the launches of a Jacobi level with d sweeps: the step that starts from zero needs no product, the others are one launch each.
 int amg_cycle(const nh_amg *h, size_t l, const double *b, double *x, hipStream_t s) {
   const nh_amg_level &lv = h->levels[l];
   const i64 n = lv.A.nrows;
@@ -333,17 +563,27 @@ int amg_cycle(const nh_amg *h, size_t l, const double *b, double *x, hipStream_t
   if (lv.kind == NH_AMG_DIAGONAL) return scale(n, lv.w_dev, b, x, s);
   const nh_amg_level &next = h->levels[l + 1];
   double *cur = lv.t_dev, *other = x;
-  if (int rc = scale(n, lv.w_dev, b, cur, s)) return rc;
-  for (int k = 1; k < lv.sweeps; ++k) {
-    if (int rc = jacobi(lv.A, cur, lv.w_dev, b, lv.rowmask_dev, other, s)) return rc;
+  const bool cheb = lv.smoother == NH_AMG_CHEBYSHEV;
+  const int sweeps = cheb ? lv.degree : lv.sweeps;
+  if (cheb) {
+    hipLaunchKernelGGL(k_chebyshev_start, dim3(vec_grid(n)), dim3(WG), 0, s, n, lv.coef_dev, lv.w_dev, b, lv.d_dev, cur);
+    NH_LAUNCH_CHECK();
+  } else if (int rc = scale(n, lv.w_dev, b, cur, s))
+    return rc;
+  for (int k = 1; k < sweeps; ++k) {
+    if (int rc = cheb ? chebyshev(lv.A, cur, lv.d_dev, lv.w_dev, b, lv.coef_dev + 2 * k, lv.rowmask_dev, other, lv.d_dev, s)
+                      : jacobi(lv.A, cur, lv.w_dev, b, lv.rowmask_dev, other, s))
+      return rc;
     std::swap(cur, other);
   }
   if (int rc = nh_csr_spmv(&lv.A, -1., cur, 1., b, lv.rowmask_dev, lv.r_dev, s)) return rc;
   if (int rc = nh_csr_spmv(&lv.R, 1., lv.r_dev, 0., nullptr, nullptr, next.b_dev, s)) return rc;
   if (int rc = amg_cycle(h, l + 1, next.b_dev, next.x_dev, s)) return rc;
   if (int rc = nh_csr_spmv(&lv.P, 1., next.x_dev, 1., cur, nullptr, cur, s)) return rc;
-  for (int k = 0; k < lv.sweeps; ++k) {
-    if (int rc = jacobi(lv.A, cur, lv.w_dev, b, lv.rowmask_dev, other, s)) return rc;
+  for (int k = 0; k < sweeps; ++k) {
+    if (int rc = cheb ? chebyshev(lv.A, cur, k ? lv.d_dev : nullptr, lv.w_dev, b, lv.coef_dev + 2 * k, lv.rowmask_dev, other, lv.d_dev, s)
+                      : jacobi(lv.A, cur, lv.w_dev, b, lv.rowmask_dev, other, s))
+      return rc;
     std::swap(cur, other);
   }
   return NH_OK;  // (cur == x)
@@ -419,6 +659,53 @@ int nh_csr_jacobi(const nh_csr *A, const double *x_dev, const double *w_dev, con
   return jacobi(*A, x_dev, w_dev, b_dev, rowmask_dev, y_dev, nh_stream(stream));
 }
 
+int nh_csr_chebyshev(const nh_csr *A, const double *x_dev, const double *d_dev, const double *dinv_dev, const double *b_dev, const double *coef_dev,
+                     const unsigned char *rowmask_dev, double *y_dev, double *dout_dev, void *stream) {
+  if (int rc = check_csr("nh_csr_chebyshev", A)) return rc;
+  NH_REQUIRE(A->nrows == A->ncols, "nh_csr_chebyshev: the matrix must be square (got %lld x %lld)", (long long)A->nrows, (long long)A->ncols);
+  NH_REQUIRE(!A->nrows || (x_dev && dinv_dev && b_dev && coef_dev && y_dev && dout_dev), "nh_csr_chebyshev: NULL vector or coefficients");
+  NH_REQUIRE(!A->nrows || (x_dev != y_dev && x_dev != dout_dev && y_dev != dout_dev && y_dev != d_dev),
+             "nh_csr_chebyshev: the result must not be the argument, nor the two results each other");
+  return chebyshev(*A, x_dev, d_dev, dinv_dev, b_dev, coef_dev, rowmask_dev, y_dev, dout_dev, nh_stream(stream));
+}
+
+int nh_csr_lanczos(const nh_csr *A, const double *s_dev, const unsigned char *rowmask_dev, const double *u_dev, int steps, double *work_dev, double *out_dev,
+                   void *stream) {
+  if (int rc = check_csr("nh_csr_lanczos", A)) return rc;
+  NH_REQUIRE(A->nrows == A->ncols, "nh_csr_lanczos: the matrix must be square (got %lld x %lld)", (long long)A->nrows, (long long)A->ncols);
+  NH_REQUIRE(steps >= 1 && steps <= 1 << 20, "nh_csr_lanczos: steps must be at least 1 (got %d)", steps);
+  NH_REQUIRE(out_dev, "nh_csr_lanczos: nowhere to put the coefficients");
+  NH_REQUIRE(!A->nrows || (s_dev && u_dev && work_dev), "nh_csr_lanczos: NULL vector or work array");
+  hipStream_t s = nh_stream(stream);
+  NH_CHECK_HIP(hipMemsetAsync(out_dev, 0, sizeof(double) * (size_t)(2 * steps + 1), s));
+  const i64 n = A->nrows;
+  if (!n) return NH_OK;
+  const int L = A->lanes ? A->lanes : nh_csr_lanes(n, A->nnz);
+  const int npa = (int)spmv_grid(n, L);
+  const unsigned grid = vec_grid(n);
+  double *q = work_dev + NH_LANCZOS_CELLS, *qprev = q + n, *w = qprev + n, *sq = w + n;
+  hipLaunchKernelGGL(k_lanczos_start, dim3(grid), dim3(WG), 0, s, n, u_dev, s_dev, rowmask_dev, q, work_dev);
+  NH_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_lanczos_first, dim3(grid), dim3(WG), 0, s, n, (int)grid, s_dev, q, sq, work_dev);
+  NH_LAUNCH_CHECK();
+  for (int j = 0; j < steps; ++j) {
+    if (A->col32_dev)
+      launch_lanczos_product(L, *A, A->col32_dev, sq, s_dev, q, rowmask_dev, w, work_dev, s);
+    else
+      launch_lanczos_product(L, *A, (const i64 *)A->colidx_dev, sq, s_dev, q, rowmask_dev, w, work_dev, s);
+    NH_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_lanczos_update, dim3(grid), dim3(WG), 0, s, n, npa, (int)(j == 0), (const double *)q, (const double *)qprev, w, work_dev);
+    NH_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_lanczos_normalize, dim3(grid), dim3(WG), 0, s, n, (int)grid, j, steps, s_dev, w, sq, work_dev, out_dev);
+    NH_LAUNCH_CHECK();
+    double *t = qprev;  // (the vectors rotate whether or not the recurrence has stopped: the launches are a function of sizes only)
+    qprev = q;
+    q = w;
+    w = t;
+  }
+  return NH_OK;
+}
+
 int nh_amg_create(const nh_amg_level *levels, int nlevels, nh_amg **out) {
   NH_REQUIRE(levels && nlevels >= 1 && out, "nh_amg_create: no levels, or nowhere to put the handle");
   for (int l = 0; l < nlevels; ++l) {
@@ -439,7 +726,12 @@ int nh_amg_create(const nh_amg_level *levels, int nlevels, nh_amg **out) {
     }
     if (lv.kind == NH_AMG_COARSEN) {
       const i64 nc = levels[l + 1].A.nrows;
-      NH_REQUIRE(lv.sweeps >= 1, "nh_amg_create: level %d: sweeps must be at least 1 (got %d)", l, lv.sweeps);
+      NH_REQUIRE(lv.smoother == NH_AMG_JACOBI || lv.smoother == NH_AMG_CHEBYSHEV, "nh_amg_create: level %d has an unknown smoother %d", l, lv.smoother);
+      if (lv.smoother == NH_AMG_CHEBYSHEV) {
+        NH_REQUIRE(lv.degree >= 1, "nh_amg_create: level %d: degree must be at least 1 (got %d)", l, lv.degree);
+        NH_REQUIRE(!n || (lv.coef_dev && lv.d_dev), "nh_amg_create: level %d lacks the coefficients or the vector d of its Chebyshev smoother", l);
+      } else
+        NH_REQUIRE(lv.sweeps >= 1, "nh_amg_create: level %d: sweeps must be at least 1 (got %d)", l, lv.sweeps);
       NH_REQUIRE(!n || (lv.t_dev && lv.r_dev), "nh_amg_create: level %d lacks its work vectors", l);
       if (int rc = check_csr("nh_amg_create (a prolongator)", &lv.P)) return rc;
       if (int rc = check_csr("nh_amg_create (a restriction)", &lv.R)) return rc;

@@ -979,10 +979,35 @@ def csr_jacobi(values, rowptr, colidx, ncols, x, w, b, *, y=None, rowmask=None, 
     return y
 
 
+def csr_chebyshev(values, rowptr, colidx, ncols, x, d, dinv, b, coef, *, y=None, dout=None, rowmask=None, col32=None, lanes=0):
+    '''(y, dout): one step of the Chebyshev smoother in one launch (nh_csr_chebyshev): dout = c1 d + c2 dinv (b - A x), y = x + dout on the rows the mask keeps,
+    0 elsewhere; `coef`: the device tensor (c1, c2).  d None: the first step of a polynomial, which reads neither d nor c1.  `dout` may be `d`.'''
+    n = rowptr.numel() - 1
+    if y is None:
+        y = device.empty(n, 'float64')
+    if dout is None:
+        dout = device.empty(n, 'float64')
+    _lib.call('nh_csr_chebyshev', ctypes.byref(_csr(values, rowptr, colidx, ncols, col32, lanes)), device.ptr(x), device.ptr(d), device.ptr(dinv), device.ptr(b),
+              device.ptr(coef), device.ptr(rowmask), device.ptr(y), device.ptr(dout), device.stream())
+    return y, dout
+
+
+def csr_lanczos(values, rowptr, colidx, ncols, s, u, steps, *, rowmask=None, col32=None, lanes=0):
+    '''enqueue `steps` steps of the Lanczos recurrence on S A_f S, S = diag(s), from the start vector u (nh_csr_lanczos); returns the device tensor of
+    2 steps + 1 doubles: alpha_j, beta_(j+1) in pairs, then the number of steps taken'''
+    n = rowptr.numel() - 1
+    out = device.empty(2 * int(steps) + 1, 'float64')
+    work = device.empty(4 * n + _lib.LANCZOS_CELLS, 'float64')
+    _lib.call('nh_csr_lanczos', ctypes.byref(_csr(values, rowptr, colidx, ncols, col32, lanes)), device.ptr(s), device.ptr(rowmask), device.ptr(u), int(steps),
+              device.ptr(work), device.ptr(out), device.stream())
+    return out
+
+
 class Amg:
     '''The handle of a hierarchy (nh_amg_create / nh_amg_free).  `levels`: one dict per level with A, and P, R for a coarsened level, as (values, rowptr,
-    colidx, ncols, col32, lanes); rowmask, w, b, x, t, r, Ainv, idx: device tensors or None; kind: 'coarsen', 'dense' or 'diagonal'; sweeps; ndense.  The
-    handle holds views: this object keeps the tensors alive.'''
+    colidx, ncols, col32, lanes); rowmask, w, b, x, t, r, Ainv, idx: device tensors or None; kind: 'coarsen', 'dense' or 'diagonal'; sweeps; ndense.  A
+    coarsened level with smoother='chebyshev' (default 'jacobi') also has degree, coef (2 degree doubles) and d, and w = 1 / diag.  The handle holds views:
+    this object keeps the tensors alive.'''
 
     def __init__(self, levels):
         self._keep = levels
@@ -993,9 +1018,12 @@ class Amg:
             for name in ('P', 'R'):
                 if d.get(name) is not None:
                     setattr(lv, name, _csr(*d[name]))
-            for name in ('rowmask', 'w', 'b', 'x', 't', 'r', 'Ainv', 'idx'):
+            for name in ('rowmask', 'w', 'b', 'x', 't', 'r', 'Ainv', 'idx', 'coef', 'd'):
                 setattr(lv, name + '_dev', device.ptr(d.get(name)))
             lv.kind, lv.sweeps, lv.ndense = _lib.AMG_KINDS[d['kind']], int(d.get('sweeps', 1)), int(d.get('ndense', 0))
+            lv.smoother, lv.degree = _lib.AMG_SMOOTHERS[d.get('smoother', 'jacobi')], int(d.get('degree', 0))
+            if lv.smoother and d['kind'] == 'coarsen' and (d['coef'].numel() != 2 * lv.degree or d['d'].numel() != d['A'][1].numel() - 1):
+                raise ValueError(f'Amg: a Chebyshev level of degree {lv.degree} needs {2 * lv.degree} coefficients and a vector d of its size')  # (the cycle reads them unchecked)
         self._handle = ctypes.c_void_p()
         _lib.call('nh_amg_create', array, len(levels), ctypes.byref(self._handle))
 

@@ -352,7 +352,11 @@ class HipMatrix:
         shape (n, k), or (n,) for k = 1, with 1 <= k <= 6 finite vectors that the smoother reduces slowly -- for elasticity the rigid-body modes
         (`amg.rigid_body_modes(coords)`), without which a vector problem gets a valid preconditioner, not an optimal one.  Rows of constrained dofs are ignored;
         a host array crosses PCIe once per solve, as n k doubles.  The symbolic phase runs once per pattern, mask, `coarse` and k and is handed on by
-        `_with_values`.
+        `_with_values`.  `preconargs` may name the smoother: `smoother='jacobi'` (the default: the `sweeps` above) or `smoother='chebyshev'` with
+        `degree=2` (1 .. 8: the steps of the polynomial before and after each coarse correction, a cycle costing what `sweeps=degree` costs), `eigsteps=10`
+        (1 .. 64: the Lanczos steps that estimate the largest eigenvalue of D^-1 A on every level, run on the device at each numeric setup) and
+        `eigratio=10.` (> 1: the polynomial damps the eigenvalues between the upper bound and its `eigratio`-th part).  `sweeps` other than 1 with 'chebyshev',
+        or one of these three keys with 'jacobi', is an error.
         `maxiter` defaults to the number of free dofs; `check`: iterations enqueued between two looks at the device's residual norm and breakdown flag (one
         16-byte copy).  Raises ToleranceNotReached(best) when the bound is not met, MatrixError when the matrix turns out not to be positive definite.
 
@@ -394,7 +398,8 @@ class HipMatrix:
             raise MatrixError(f"solver {solver!r} needs a tolerance: pass atol or rtol (an iterative solve has no machine-precision mode)")
         if precon == 'amg' and solver == 'cg':
             from . import amg
-            preconargs = amg.check_args(preconargs, ncols)
+            preconargs, smoother = amg.split_smoother(preconargs)
+            preconargs = amg.check_args(preconargs, ncols) + (smoother,)
         elif precon not in ('diag', None):
             raise MatrixError(f"invalid preconditioner {precon!r} for HipMatrix solver {solver!r}: 'diag' or None" + (", or 'amg'" if solver == 'cg' else ''))
         elif preconargs is not None:
@@ -434,9 +439,9 @@ class HipMatrix:
             dinv = (1. / diag).masked_fill(~keep | (diag == 0), 0.)  # (constrained rows: any finite number, their residual is zero)
         return mask, x, b, dinv
 
-    def _amg_hierarchy(self, free, mask, coarse, sweeps, nullspace=None):
+    def _amg_hierarchy(self, free, mask, coarse, sweeps, nullspace=None, smoother=None):
         '''the hierarchy of an 'amg' preconditioner (amg.Hierarchy): the symbolic phase is taken from the cache if it was made for this mask, this `coarse` and
-        this number of near-nullspace vectors, the numeric phase runs on the values of this matrix'''
+        this number of near-nullspace vectors, the numeric phase runs on the values of this matrix (the smoother belongs to it: the cache does not know it)'''
         from . import amg, device
         _, rowptr, colidx = self.triplet()
         k = None if nullspace is None else nullspace.shape[1]
@@ -444,7 +449,7 @@ class HipMatrix:
             self._amg = free.copy(), coarse, k, amg.symbolic(rowptr, colidx, None if mask is None else mask != 0, coarse, k)
         if nullspace is not None:  # PCIe: a host array goes up once, n k doubles
             nullspace = nullspace.contiguous() if _is_tensor(nullspace) else device.to_dev(nullspace, 'float64')
-        return amg.Hierarchy(self._amg[3], self.triplet()[0], sweeps, nullspace)
+        return amg.Hierarchy(self._amg[3], self.triplet()[0], sweeps, nullspace, smoother)
 
     def _cg(self, rhs, free, lhs, atol, rtol, precon, maxiter, check, on_device, preconargs=None):
         from . import device, kernels

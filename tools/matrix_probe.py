@@ -17,9 +17,14 @@
   * for the smoothed-aggregation AMG preconditioner (precon='amg'): the time of the symbolic and of the numeric phase of its setup, level sizes and operator
     complexity, one cycle against one masked product, and iterations, wall time and true residual of an AMG-CG solve (with the symbolic phase, and with it
     cached) beside the Jacobi-CG solve of the same system in the same process; for the vector matrices (elasticity96, p2vector32) all of that once more with
-    the rigid-body modes as the near-nullspace (preconargs=dict(nullspace=amg.rigid_body_modes(coords))).
+    the rigid-body modes as the near-nullspace (preconargs=dict(nullspace=amg.rigid_body_modes(coords))),
+  * for the smoothers of that preconditioner (section 'smoother'; the rigid-body modes for the vector matrices), in one process and alternating: Jacobi with one
+    (the default) and two sweeps and Chebyshev of degree 2 and 3 -- the numeric setup with the share of its Lanczos estimates, the bounds of every level, one
+    cycle, and iterations and wall time of the solve to rtol = 1e-8 with the symbolic phase cached; with --eigratios 4,10,30 the Chebyshev degree-2 solve for
+    each ratio, and with --eigsteps 5,10,20 for each number of Lanczos steps.
 
-Usage: python tools/matrix_probe.py [--matrices poisson128,elasticity96,bilinear2048,bilinear1024,p2vector32] [--scale 1.0] [--sections spmv,cg,bicgstab,fgmres,amg] [--out FILE]
+Usage: python tools/matrix_probe.py [--matrices poisson128,elasticity96,elasticity64,elasticity48,bilinear2048,bilinear1024,p2vector32,p2vector16] [--scale 1.0]
+[--sections spmv,cg,bicgstab,fgmres,amg,smoother] [--eigratios 4,10,30] [--eigsteps 5,10,20] [--out FILE]
 (--scale shrinks every mesh for a quick look; --sections leaves parts out).  Not run by any test.'''
 import argparse
 import json
@@ -39,14 +44,14 @@ def build(name, scale):
     n = lambda full: max(2, int(round(full * scale)))
     if name == 'poisson128':
         shape, degree, vector = [n(128)] * 3, 1, False
-    elif name == 'elasticity96':
-        shape, degree, vector = [n(96)] * 3, 1, True
+    elif name in ('elasticity96', 'elasticity64', 'elasticity48'):
+        shape, degree, vector = [n(int(name[10:]))] * 3, 1, True
     elif name == 'bilinear2048':
         shape, degree, vector = [n(2048)] * 2, 1, False
     elif name == 'bilinear1024':
         shape, degree, vector = [n(1024)] * 2, 1, False
-    elif name == 'p2vector32':
-        shape, degree, vector = [n(32)] * 3, 2, True
+    elif name in ('p2vector32', 'p2vector16'):
+        shape, degree, vector = [n(int(name[8:]))] * 3, 2, True
     else:
         raise SystemExit(f'unknown matrix {name!r}')
     domain, geom = mesh.rectilinear([numpy.linspace(0, 1, m + 1) for m in shape])
@@ -149,6 +154,8 @@ def probe(name, args):
         info['fgmres'] = probe_fgmres(A, free, mask, rhs_dev, res0, args)
     if 'amg' in args.sections:
         info['amg'] = probe_amg(A, free, mask, rhs_dev, res0, info, args)
+    if 'smoother' in args.sections:
+        info['smoother'] = probe_smoother(A, free, mask, rhs_dev, res0, info, args)
     return info
 
 
@@ -309,6 +316,70 @@ def probe_amg(A, free, mask, rhs_dev, res0, info, args):
     return out
 
 
+def probe_smoother(A, free, mask, rhs_dev, res0, info, args):
+    '''the smoothers of precon='amg' side by side on one hierarchy: per configuration the numeric setup (wall clock, synchronised, the median of three after
+    a first), for Chebyshev the part of it that is nh_csr_lanczos (HIP events around the calls of a setup's worth of levels) and the bounds, one cycle, and the
+    solve (the symbolic phase cached; the median of three, the configurations alternating)'''
+    import torch
+    from nutils_amd import amg, device, kernels, matrix
+    values, rowptr, colidx = A.triplet()
+    B = device.to_dev(amg.rigid_body_modes(nodes_of(info)), 'float64') if info['components'] > 1 else None
+    base = {} if B is None else dict(nullspace=B)
+    cheb = lambda **kwargs: dict(base, smoother='chebyshev', **kwargs)
+    configs = {'jacobi1': dict(base), 'jacobi2': dict(base, sweeps=2), 'chebyshev2': cheb(degree=2), 'chebyshev3': cheb(degree=3)}
+    for ratio in args.eigratios:
+        configs[f'chebyshev2_ratio{ratio:g}'] = cheb(degree=2, eigratio=ratio)
+    for steps in args.eigsteps:
+        configs[f'chebyshev2_steps{steps}'] = cheb(degree=2, eigsteps=steps)
+
+    def clocked(fn):
+        device.synchronize()
+        t0 = time.perf_counter()
+        result = fn()
+        device.synchronize()
+        return result, (time.perf_counter() - t0) * 1e3
+
+    try:
+        levels = amg.symbolic(rowptr, colidx, mask != 0, 256, None if B is None else B.shape[1])
+    except (matrix.MatrixError, RuntimeError) as e:  # (recorded, not hidden)
+        return dict(error=f'{type(e).__name__}: {e}')
+    out = dict(levels=[lv.nfree for lv in levels], kinds=[lv.kind for lv in levels])
+    r = torch.where(mask != 0, torch.from_numpy(numpy.random.default_rng(1).normal(size=A.shape[0])).cuda(), torch.zeros_like(rhs_dev))
+    z = torch.empty_like(r)
+    for name, preconargs in configs.items():
+        rest, smoother = amg.split_smoother(preconargs)
+        sweeps = amg.check_args(rest, A.shape[0])[1]
+        make = lambda: amg.Hierarchy(levels, values, sweeps, B, smoother)
+        h, first = clocked(make)
+        res = out[name] = dict(numeric_first_ms=first, numeric_ms=float(numpy.median([clocked(make)[1] for _ in range(3)])))
+        if smoother is not None:
+            res.update(theta=[d.theta for d in h.data[:-1]], rho=[float(d.rho) for d in h.data[:-1]], ub=[d.ub for d in h.data[:-1]], eigsteps_taken=[d.eigsteps for d in h.data[:-1]])
+            coarsened = [(lv, d, d.dinv.sqrt(), amg.start_vector(lv.n, values.device)) for lv, d in zip(levels[:-1], h.data[:-1])]
+            estimate = lambda: [kernels.csr_lanczos(d.values, lv.rowptr, lv.colidx, lv.n, s, u, smoother['eigsteps'], rowmask=lv.mask, col32=lv.col32) for lv, d, s, u in coarsened]
+            res['lanczos_ms'] = stats(windows([estimate], args.window)[0])['us'] * 1e-3
+        res['cycle'] = stats(windows([lambda: h.apply(r, z)], args.window)[0])
+        del h
+
+    def solve(name):
+        try:
+            return A.solve(rhs_dev, constrain=~free, rtol=1e-8, maxiter=args.maxiter, precon='amg', preconargs=configs[name]), True
+        except matrix.ToleranceNotReached as e:
+            return e.best, False
+
+    A._amg = None
+    runs = {name: [clocked(lambda: solve(name))] for name in configs}  # (the first of them runs the symbolic phase, which the matrix then keeps)
+    for _ in range(3):  # (alternating)
+        for name in configs:
+            runs[name].append(clocked(lambda: solve(name)))
+    for name, timed in runs.items():
+        (sol, converged), _ = timed[0]
+        solve(name)
+        ms = [t for _, t in timed[1:]]
+        out[name]['solve'] = dict(converged=converged, iterations=A.iterations, wall_ms=float(numpy.median(ms)), spread=max(ms) - min(ms),
+                                  true_relative_residual=float(A.spmv(sol, alpha=-1., beta=1., b=rhs_dev, rowmask=mask).norm() / res0.norm()))
+    return out
+
+
 BICGSTAB_STEPS = 20
 
 
@@ -465,9 +536,13 @@ def main():
     ap.add_argument('--maxiter', type=int, default=20000)
     ap.add_argument('--no-host-solve', action='store_true', help='skip the host BiCGStab of the nonsymmetric twin (minutes for the large matrices)')
     ap.add_argument('--sections', default='spmv,cg,bicgstab,fgmres,amg', help='the parts of the probe to run')
+    ap.add_argument('--eigratios', default='', help="section 'smoother': the eigratio values of further Chebyshev degree-2 rows, e.g. 4,10,30")
+    ap.add_argument('--eigsteps', default='', help="section 'smoother': the eigsteps values of further Chebyshev degree-2 rows, e.g. 5,10,20")
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     args.sections = args.sections.split(',')
+    args.eigratios = [float(v) for v in args.eigratios.split(',') if v]
+    args.eigsteps = [int(v) for v in args.eigsteps.split(',') if v]
     import torch
     out = open(args.out, 'a') if args.out else None
     for name in args.matrices.split(','):
