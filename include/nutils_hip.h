@@ -739,6 +739,26 @@ int nh_csr_spmv_dots(const nh_csr *A, const double *x_dev, const double *w_dev, 
 int nh_bicgstab_init(int64_t n, const double *dinv_dev, const double *r_dev, double *rhat_dev, double *p_dev, double *phat_dev, double *work_dev, void *stream);
 int nh_bicgstab_iterate(const nh_csr *A, const unsigned char *rowmask_dev, const double *dinv_dev, double *x_dev, double *r_dev, const double *rhat_dev, double *p_dev,
                         double *v_dev, double *s_dev, double *t_dev, double *phat_dev, double *shat_dev, double *work_dev, double stop_rr, int niter, void *stream);
+/* MINRES (Paige and Saunders) for SYMMETRIC square A, definite or not, preconditioned with M^-1 = dinv > 0 (the inverse of |diag|, say) or the identity (dinv_dev
+ * NULL), entirely on the device and by the rules of the CG above: constraints are a row mask on which every vector vanishes, nothing is atomic, every sum in
+ * a fixed order, no scalar visits the host, repeated solves are bit-identical.  One product and three launches an iteration, in the variable names of
+ * scipy.sparse.linalg.minres: q = mask(A v) with the partials of v . q; alpha = v . q, r1 <- r2, r2 <- q - (beta / oldb) r1 - (alpha / beta) r2 (no r1 term in
+ * the first step), partials of r2 . dinv r2; beta' = sqrt(r2 . dinv r2), the rotation, w1 <- w2, w2 <- (v - oldeps w1 - delta w2) / gamma, x += phi w2,
+ * r <- sn^2 r - (phibar cs / beta') r2, v <- dinv r2 / beta', partials of r . r.  phibar is the norm of the residual in the M^-1-norm; r carries the residual itself,
+ * since it is the 2-norm that stops the iteration.  Symmetry is not checked: on a nonsymmetric A the recurrence's r is not the residual of x.
+ * nh_minres_init takes a given r (which stays the caller's: it becomes the carried residual) and sets r1 = r2 = r, w1 = w2 = 0, v = dinv r / sqrt(r . dinv r), the
+ * scalars, work[0 .. 2]; it marks the iteration as finished if r = 0 and raises the flag if r . dinv r is not positive.  nh_minres_iterate enqueues niter
+ * iterations and one small launch that sums r . r.  Once the recurrence has r . r <= stop_rr every remaining iteration leaves all vectors as they are, but for
+ * the one product that follows the deciding step, which writes q and nothing else.  work_dev: nh_minres_work_doubles() doubles, of which the host reads
+ * work[0] = r . r of the recurrence, work[1] = flag (0. / 1.), work[2] = iterations since nh_minres_init that moved x (exact, whatever niter was).  The flag is
+ * raised, with r != 0, when a scalar is not finite, r2 . dinv r2 < 0 (dinv is not positive) or gamma = 0; x and r are then those of the last complete iteration
+ * and later iterations do no arithmetic.  beta' = 0 with gamma > 0 is the Krylov space exhausted: the step is taken, r becomes 0, the iteration stops, no flag.
+ * Vectors: x, r in/out; r1, r2, v, q, w1, w2 belong to the iteration between init and the last iterate; dinv must be finite on masked rows. */
+int64_t nh_minres_work_doubles(void);
+int nh_minres_init(int64_t n, const double *dinv_dev, const double *r_dev, double *r1_dev, double *r2_dev, double *v_dev, double *w1_dev, double *w2_dev, double *work_dev,
+                   void *stream);
+int nh_minres_iterate(const nh_csr *A, const unsigned char *rowmask_dev, const double *dinv_dev, double *x_dev, double *r_dev, double *r1_dev, double *r2_dev, double *v_dev,
+                      double *q_dev, double *w1_dev, double *w2_dev, double *work_dev, double stop_rr, int niter, void *stream);
 /* Restarted GMRES for ANY square A, right-preconditioned with M^-1 = dinv (Jacobi) or the identity (dinv_dev NULL; with a fixed M this is also flexible GMRES),
  * entirely on the device and by the rules above: a row mask on which every vector vanishes, nothing atomic, every sum in a fixed order, no scalar visits the
  * host, repeated solves are bit-identical.  V_dev: restart + 1 basis vectors of n doubles, one after the other; z_dev, w_dev: n doubles; work_dev:

@@ -216,6 +216,9 @@ SIGNATURES = {
     'nh_csr_spmv_dots': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, vp, vp, vp, vp]),
     'nh_bicgstab_init': (ctypes.c_int, [c_i64, vp, vp, vp, vp, vp, vp, vp]),
     'nh_bicgstab_iterate': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_double, ctypes.c_int, vp]),
+    'nh_minres_work_doubles': (c_i64, []),
+    'nh_minres_init': (ctypes.c_int, [c_i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    'nh_minres_iterate': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_double, ctypes.c_int, vp]),
     'nh_gmres_work_doubles': (c_i64, [ctypes.c_int]),
     'nh_gmres_init': (ctypes.c_int, [c_i64, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
     'nh_gmres_iterate': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, vp]),

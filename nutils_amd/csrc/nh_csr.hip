@@ -20,6 +20,8 @@
 //     per kernel, so no kernel reads a cell that one of its own workgroups writes.
 //   * k_bicgstab_half / k_bicgstab_update / k_bicgstab_direction: the vector part of a right-preconditioned BiCGStab step for general square matrices, by
 //     the same rules (the cells and who writes them: the B_ enum below).
+//   * k_minres_lanczos / k_minres_update: the vector part of a MINRES step for symmetric indefinite matrices, one product and three launches a step, by the
+//     same rules (the M_ enum below).
 #include "nh_common.h"
 #include <algorithm>
 #include <climits>
@@ -388,6 +390,206 @@ __global__ __launch_bounds__(WG) void k_spmv_dots_sum(int nwy, double *work) {
   if (threadIdx.x == 0) {
     work[0] = wy;
     work[1] = yy;
+  }
+}
+
+// ---- MINRES (Paige and Saunders) for symmetric matrices, definite or not, in the variable names of scipy.sparse.linalg.minres; M^-1 = dinv > 0 or the identity;
+// all vectors vanish on masked rows.  The y of the textbook is not stored: it is dinv r2.  An iteration is
+//   q = mask(A v), partials of v . q                                                (k_csr_spmv, DOT = 2, w = v)
+//   lanczos:   alpha = v . q;  r1 <- r2;  r2 <- q - (beta / oldb) r1 - (alpha / beta) r2 (no r1 term in the first step);  partials of r2 . dinv r2
+//   update:    beta' = sqrt(r2 . dinv r2);  the rotation (delta, gbar, epsln, dbar, gamma, cs, sn, phi, phibar);  w1 <- w2;  w2 <- (v - oldeps w1 - delta w2) / gamma;
+//              x += phi w2;  r <- sn^2 r - (phibar cs / beta') r2;  v <- dinv r2 / beta';  partials of r . r
+// and every nh_minres_iterate ends with k_minres_finish, one workgroup that sums the partials of r . r for the host.  phibar is the residual norm in the M^-1-norm;
+// r carries the residual itself, whose 2-norm the stopping rule is about.  It is the lanczos kernel that finds r . r <= stop_rr, one product late: that product
+// writes q and nothing else.  Cells of the work array; after "<-" the kernel that writes a cell, every other kernel only reads it (the init writes all).  What
+// crosses an iteration is written by update and relayed by lanczos to the cell that update reads.  A status is 0 (iterate), ST_DONE (r . r <= stop_rr, or beta' =
+// 0: the Krylov space is exhausted, the step taken) or ST_BAD (a scalar that is not finite, r2 . dinv r2 < 0, gamma = 0); it travels update -> product and
+// lanczos, lanczos -> update, and a kernel that receives a non-zero status passes it on and does nothing else.
+enum {
+  M_RR = 0,      // r . r of the recurrence        <- finish
+  M_FLAG = 1,    // 1. after ST_BAD                <- finish
+  M_COUNT = 2,   // iterations that moved x        <- finish
+  M_ST = 3,      // status for product and lanczos <- update
+  M_BETA = 4,    // the beta that v was divided by <- update
+  M_OLDB = 5,    // the beta before it             <- update
+  M_DBAR = 6,    //                                <- update
+  M_EPSLN = 7,   //                                <- update
+  M_PHIBAR = 8,  //                                <- update
+  M_CS = 9,      //                                <- update
+  M_SN = 10,     //                                <- update
+  M_COUNT_U = 11,  // iterations that moved x      <- update
+  M_FLAG_U = 12,   // 1. after ST_BAD              <- update
+  M_ST_L = 16,   // status for update              <- lanczos
+  M_ALPHA = 17,  // v . q                          <- lanczos
+  M_RELAY = 18,  // M_BETA .. M_COUNT_U, relayed   <- lanczos
+  M_NRELAY = M_COUNT_U - M_BETA + 1,
+  M_VQ = 32,                    // partials of v . q of the product
+  M_QQ = M_VQ + SPMV_MAX_WGS,   // partials of q . q of the product (not read)
+  M_RYP = M_QQ + SPMV_MAX_WGS,  // partials of r2 . dinv r2 <- lanczos
+  M_RRP = M_RYP + VEC_MAX_WGS,  // partials of r . r        <- update
+  M_END = M_RRP + VEC_MAX_WGS
+};
+
+// r1 = r2 = r, w1 = w2 = 0, partials of r . dinv r and r . r
+__global__ __launch_bounds__(WG) void k_minres_init(i64 n, double *work, const double *__restrict__ dinv, const double *__restrict__ r, double *__restrict__ r1,
+                                                    double *__restrict__ r2, double *__restrict__ w1, double *__restrict__ w2) {
+  __shared__ double lds[4];
+  double ry = 0, rr = 0;
+  for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < n; i += (i64)gridDim.x * WG) {
+    const double ri = r[i];
+    r1[i] = r2[i] = ri;
+    w1[i] = w2[i] = 0.;
+    ry += ri * (dinv ? dinv[i] * ri : ri);
+    rr += ri * ri;
+  }
+  ry = block_sum(ry, lds);
+  rr = block_sum(rr, lds);
+  if (threadIdx.x == 0) {
+    work[M_RYP + blockIdx.x] = ry;
+    work[M_RRP + blockIdx.x] = rr;
+  }
+}
+
+__global__ __launch_bounds__(WG) void k_minres_init_scalars(int nparts, double *work) {
+  __shared__ double lds[4];
+  const double ry = partial_sum(work + M_RYP, nparts, lds);
+  const double rr = partial_sum(work + M_RRP, nparts, lds);
+  if (threadIdx.x == 0) {
+    const bool bad = !(finite(rr) && finite(ry) && (ry > 0. || (ry == 0. && rr == 0.)));  // (r . dinv r <= 0 with r != 0: the preconditioner is not positive)
+    const double beta = bad ? 0. : sqrt(ry);
+    work[M_RR] = rr;
+    work[M_FLAG] = work[M_FLAG_U] = bad ? 1. : 0.;
+    work[M_COUNT] = work[M_COUNT_U] = 0.;
+    work[M_ST] = bad ? ST_BAD : rr == 0. ? ST_DONE : 0.;  // (a residual of zero: nothing to do, and nothing to normalise)
+    work[M_BETA] = work[M_PHIBAR] = beta;
+    work[M_OLDB] = work[M_DBAR] = work[M_EPSLN] = work[M_SN] = 0.;
+    work[M_CS] = -1.;
+  }
+}
+
+// v = dinv r / beta: the first Lanczos vector
+__global__ __launch_bounds__(WG) void k_minres_first(i64 n, const double *__restrict__ work, const double *__restrict__ dinv, const double *__restrict__ r,
+                                                     double *__restrict__ v) {
+  if (work[M_ST] != 0.) return;
+  const double beta = work[M_BETA];
+  for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < n; i += (i64)gridDim.x * WG) v[i] = (dinv ? dinv[i] * r[i] : r[i]) / beta;
+}
+
+// reads ST, BETA .. COUNT_U, the v . q and r . r partials; writes ST_L, ALPHA, the relay, the r2 . dinv r2 partials
+__global__ __launch_bounds__(WG) void k_minres_lanczos(i64 n, int nvq, int nparts, double stop_rr, double *work, const double *__restrict__ dinv,
+                                                       const double *__restrict__ q, double *__restrict__ r1, double *__restrict__ r2) {
+  __shared__ double lds[4];
+  const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+  double st = work[M_ST];
+  double alpha = 0;
+  if (st == 0.) {  // (the same sums in every workgroup: the branches are uniform over the grid)
+    if (partial_sum(work + M_RRP, nparts, lds) <= stop_rr) {
+      st = ST_DONE;
+    } else {
+      alpha = partial_sum(work + M_VQ, nvq, lds);
+      if (!finite(alpha)) st = ST_BAD;
+    }
+  }
+  if (first) work[M_ST_L] = st;
+  if (st != 0.) return;
+  const double beta = work[M_BETA], oldb = work[M_OLDB];
+  if (first) {
+    work[M_ALPHA] = alpha;
+    for (int c = 0; c < M_NRELAY; ++c) work[M_RELAY + c] = work[M_BETA + c];
+  }
+  const bool second = oldb != 0.;  // from the second step on: r1 of the first is r2
+  const double c1 = second ? beta / oldb : 0., c2 = alpha / beta;
+  double ry = 0;
+  for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < n; i += (i64)gridDim.x * WG) {
+    const double r2i = r2[i];
+    double yi = q[i];
+    if (second) yi -= c1 * r1[i];
+    yi -= c2 * r2i;
+    r1[i] = r2i;
+    r2[i] = yi;
+    ry += yi * (dinv ? dinv[i] * yi : yi);
+  }
+  ry = block_sum(ry, lds);
+  if (threadIdx.x == 0) work[M_RYP + blockIdx.x] = ry;
+}
+
+// reads ST_L, ALPHA, the relay, the r2 . dinv r2 partials; writes ST, BETA .. COUNT_U, FLAG_U, the r . r partials
+__global__ __launch_bounds__(WG) void k_minres_update(i64 n, int nparts, double *work, const double *__restrict__ dinv, double *__restrict__ x, double *__restrict__ r,
+                                                      const double *__restrict__ r2, double *__restrict__ v, double *__restrict__ w1, double *__restrict__ w2) {
+  __shared__ double lds[4];
+  const bool first = blockIdx.x == 0 && threadIdx.x == 0;
+  const double st = work[M_ST_L];
+  if (st != 0.) {
+    if (first) {
+      work[M_ST] = st;
+      if (st == ST_BAD) work[M_FLAG_U] = 1.;
+    }
+    return;
+  }
+  const double ry = partial_sum(work + M_RYP, nparts, lds);
+  const double *relay = work + M_RELAY - M_BETA;
+  const double alpha = work[M_ALPHA], beta = relay[M_BETA], cs_old = relay[M_CS], sn_old = relay[M_SN], dbar_old = relay[M_DBAR], oldeps = relay[M_EPSLN];
+  bool bad = !(finite(ry) && ry >= 0.);
+  const double betan = bad ? 0. : sqrt(ry);
+  const double delta = cs_old * dbar_old + sn_old * alpha, gbar = sn_old * dbar_old - cs_old * alpha;
+  const double gamma = hypot(gbar, betan);
+  bad = bad || !(gamma > 0. && finite(gamma));
+  double cs = 0, sn = 0, phi = 0, phibar = 0;
+  if (!bad) {
+    cs = gbar / gamma;
+    sn = betan / gamma;
+    phi = cs * relay[M_PHIBAR];
+    phibar = sn * relay[M_PHIBAR];
+    bad = !(finite(phi) && finite(delta));
+  }
+  if (bad) {
+    if (first) {
+      work[M_ST] = ST_BAD;
+      work[M_FLAG_U] = 1.;
+    }
+    return;
+  }
+  const bool more = betan != 0.;  // (beta' = 0 with gamma > 0: the Krylov space is exhausted; the step is taken, r becomes 0, and there is no next v)
+  if (first) {
+    work[M_ST] = more ? 0. : ST_DONE;
+    work[M_BETA] = betan;
+    work[M_OLDB] = beta;
+    work[M_DBAR] = -cs_old * betan;
+    work[M_EPSLN] = sn_old * betan;
+    work[M_PHIBAR] = phibar;
+    work[M_CS] = cs;
+    work[M_SN] = sn;
+    work[M_COUNT_U] = relay[M_COUNT_U] + 1.;
+  }
+  const double s2 = sn * sn, c3 = more ? phibar * cs / betan : 0.;
+  double rr = 0;
+  for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < n; i += (i64)gridDim.x * WG) {
+    const double w2i = w2[i];
+    const double wi = (v[i] - oldeps * w1[i] - delta * w2i) / gamma;
+    w1[i] = w2i;
+    w2[i] = wi;
+    x[i] += phi * wi;
+    double ri = s2 * r[i];
+    if (more) {
+      const double r2i = r2[i];
+      ri -= c3 * r2i;
+      v[i] = (dinv ? dinv[i] * r2i : r2i) / betan;
+    }
+    r[i] = ri;
+    rr += ri * ri;
+  }
+  rr = block_sum(rr, lds);
+  if (threadIdx.x == 0) work[M_RRP + blockIdx.x] = rr;
+}
+
+// what the host reads, after the last iteration of a call: r . r from the partials in the order of k_minres_lanczos, the flag and the count
+__global__ __launch_bounds__(WG) void k_minres_finish(int nparts, double *work) {
+  __shared__ double lds[4];
+  const double rr = partial_sum(work + M_RRP, nparts, lds);
+  if (threadIdx.x == 0) {
+    work[M_RR] = rr;
+    work[M_FLAG] = work[M_FLAG_U];
+    work[M_COUNT] = work[M_COUNT_U];
   }
 }
 
@@ -1003,6 +1205,58 @@ int nh_bicgstab_iterate(const nh_csr *A, const unsigned char *rowmask_dev, const
     hipLaunchKernelGGL(k_bicgstab_direction, dim3(grid), dim3(WG), 0, s, n, (int)grid, stop_rr, work_dev, dinv_dev, (const double *)r_dev, (const double *)v_dev, p_dev, phat_dev);
     NH_LAUNCH_CHECK();
   }
+  return NH_OK;
+}
+
+int64_t nh_minres_work_doubles(void) { return M_END; }
+
+int nh_minres_init(int64_t n, const double *dinv_dev, const double *r_dev, double *r1_dev, double *r2_dev, double *v_dev, double *w1_dev, double *w2_dev, double *work_dev,
+                   void *stream) {
+  NH_REQUIRE(n >= 0, "nh_minres_init: negative size");
+  NH_REQUIRE(work_dev && (!n || (r_dev && r1_dev && r2_dev && v_dev && w1_dev && w2_dev)), "nh_minres_init: NULL vector");
+  hipStream_t s = nh_stream(stream);
+  const unsigned grid = vec_grid(n);
+  if (n) {
+    hipLaunchKernelGGL(k_minres_init, dim3(grid), dim3(WG), 0, s, (i64)n, work_dev, dinv_dev, r_dev, r1_dev, r2_dev, w1_dev, w2_dev);
+    NH_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_minres_init_scalars, dim3(1), dim3(WG), 0, s, (int)grid, work_dev);
+  NH_LAUNCH_CHECK();
+  if (n) {
+    hipLaunchKernelGGL(k_minres_first, dim3(grid), dim3(WG), 0, s, (i64)n, (const double *)work_dev, dinv_dev, r_dev, v_dev);
+    NH_LAUNCH_CHECK();
+  }
+  return NH_OK;
+}
+
+int nh_minres_iterate(const nh_csr *A, const unsigned char *rowmask_dev, const double *dinv_dev, double *x_dev, double *r_dev, double *r1_dev, double *r2_dev, double *v_dev,
+                      double *q_dev, double *w1_dev, double *w2_dev, double *work_dev, double stop_rr, int niter, void *stream) {
+  if (int rc = check_csr("nh_minres_iterate", A)) return rc;
+  NH_REQUIRE(A->nrows == A->ncols, "nh_minres_iterate: the matrix must be square (got %lld x %lld)", (long long)A->nrows, (long long)A->ncols);
+  NH_REQUIRE(niter >= 0, "nh_minres_iterate: negative iteration count");
+  NH_REQUIRE(stop_rr >= 0., "nh_minres_iterate: the bound on r . r must not be negative");
+  NH_REQUIRE(work_dev && (!A->nrows || (x_dev && r_dev && r1_dev && r2_dev && v_dev && q_dev && w1_dev && w2_dev)), "nh_minres_iterate: NULL vector");
+  if (!A->nrows) return NH_OK;
+  hipStream_t s = nh_stream(stream);
+  const i64 n = A->nrows;
+  nh_csr B = *A;
+  B.lanes = A->lanes ? A->lanes : nh_csr_lanes(A->nrows, A->nnz);
+  const int nvq = (int)spmv_grid(n, B.lanes);
+  const unsigned grid = vec_grid(n);
+  Epilogue vq;  // w = x = v: the partials of v . q (and of q . q, which nothing reads)
+  vq.partial = work_dev + M_VQ;
+  vq.partial2 = work_dev + M_QQ;
+  vq.w = v_dev;
+  vq.skip = work_dev + M_ST;
+  for (int it = 0; it < niter; ++it) {
+    if (int rc = spmv(&B, 1., v_dev, 0., nullptr, rowmask_dev, q_dev, vq, s)) return rc;
+    hipLaunchKernelGGL(k_minres_lanczos, dim3(grid), dim3(WG), 0, s, n, nvq, (int)grid, stop_rr, work_dev, dinv_dev, (const double *)q_dev, r1_dev, r2_dev);
+    NH_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_minres_update, dim3(grid), dim3(WG), 0, s, n, (int)grid, work_dev, dinv_dev, x_dev, r_dev, (const double *)r2_dev, v_dev, w1_dev, w2_dev);
+    NH_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_minres_finish, dim3(1), dim3(WG), 0, s, (int)grid, work_dev);
+  NH_LAUNCH_CHECK();
   return NH_OK;
 }
 

@@ -911,6 +911,23 @@ def bicgstab_iterate(values, rowptr, colidx, ncols, *, rowmask, dinv, x, r, rhat
               device.stream())
 
 
+def minres_work():
+    '''the work array of a MINRES solve (nh_minres_work_doubles): [0] = r . r of the recurrence, [1] = flag, [2] = iterations since `minres_init` that moved x'''
+    return device.empty(_lib.load().nh_minres_work_doubles(), 'float64')
+
+
+def minres_init(dinv, r, r1, r2, v, w1, w2, work):
+    '''r1 = r2 = r, w1 = w2 = 0, v = dinv r / sqrt(r . dinv r), first r . r, flag and count cleared (nh_minres_init); `dinv` is positive, or None'''
+    _lib.call('nh_minres_init', r.numel(), device.ptr(dinv), device.ptr(r), device.ptr(r1), device.ptr(r2), device.ptr(v), device.ptr(w1), device.ptr(w2), device.ptr(work),
+              device.stream())
+
+
+def minres_iterate(values, rowptr, colidx, ncols, *, rowmask, dinv, x, r, r1, r2, v, q, w1, w2, work, stop_rr, niter, col32=None, lanes=0):
+    '''enqueue `niter` MINRES iterations (nh_minres_iterate): three launches each and one at the end, nothing read back; they stop moving once r . r <= stop_rr'''
+    _lib.call('nh_minres_iterate', ctypes.byref(_csr(values, rowptr, colidx, ncols, col32, lanes)), device.ptr(rowmask), device.ptr(dinv), device.ptr(x), device.ptr(r),
+              device.ptr(r1), device.ptr(r2), device.ptr(v), device.ptr(q), device.ptr(w1), device.ptr(w2), device.ptr(work), float(stop_rr), int(niter), device.stream())
+
+
 GMRES_CHUNK = 8  # GS_CHUNK of nh_csr.hip: basis vectors the Gram-Schmidt kernels take per pass over w
 
 

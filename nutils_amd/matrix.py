@@ -8,14 +8,15 @@ conditions) is the reference's.
 
 Two backends.  'scipy' (the default; 'auto' means the same) wraps the host copy
 of the triplet in a ``ScipyMatrix`` with a direct solver.  'hip' keeps the
-triplet in HBM as a ``HipMatrix``: products, the diagonal and three Jacobi-
+triplet in HBM as a ``HipMatrix``: products, the diagonal and four Jacobi-
 preconditioned Krylov solves -- conjugate gradients ('cg') for symmetric
-positive definite systems, BiCGStab ('bicgstab') and restarted GMRES
-('fgmres') for any square matrix -- run on the device (nh_csr.hip); ``function.eval(function.as_matrix(K))`` builds
+positive definite systems, MINRES ('minres') for symmetric indefinite ones,
+BiCGStab ('bicgstab') and restarted GMRES ('fgmres') for any square matrix --
+run on the device (nh_csr.hip); ``function.eval(function.as_matrix(K))`` builds
 one without the triplet ever visiting the host, and so does ``solver.System``
 under this backend (``assemble_device``).  What a ``HipMatrix`` does
 through scipy and a re-upload -- ``submatrix``, ``T``, every solver other than
-'cg', 'bicgstab' and 'fgmres', sums of matrices with different patterns -- says so in its
+'cg', 'minres', 'bicgstab' and 'fgmres', sums of matrices with different patterns -- says so in its
 docstring.
 '''
 
@@ -169,7 +170,9 @@ class HipMatrix:
     (12 instead of 16 bytes per entry; matrices with more than 2^31 - 1 columns keep the int64 indices).
 
     On the device: products (nh_csr_spmv), the diagonal, `rowsupp` / `colsupp` (nh_csr_support), scalar multiples, sums of matrices that share their index tensors, `solve(solver='cg')`, a
-    conjugate-gradient iteration for SYMMETRIC POSITIVE DEFINITE systems preconditioned by Jacobi or by a smoothed-aggregation multigrid cycle (`precon='amg'`, amg.py), and for ANY square system (nonsymmetric, indefinite)
+    conjugate-gradient iteration for SYMMETRIC POSITIVE DEFINITE systems preconditioned by Jacobi or by a smoothed-aggregation multigrid cycle (`precon='amg'`, amg.py), for SYMMETRIC systems that are indefinite (saddle points, Helmholtz) `solve(solver='minres')`, a MINRES iteration
+    preconditioned by 1 / |diag|: one product a step, a residual that never rises in the norm it minimises, no breakdown short of the exhausted Krylov space;
+    and for ANY square system (nonsymmetric, indefinite)
     `solve(solver='bicgstab')`, a Jacobi-preconditioned BiCGStab iteration, and `solve(solver='fgmres')`, Jacobi-preconditioned restarted GMRES, whose residual
     norm never rises within a cycle; all with ONE right-hand side.  `iterations` is the iteration count of the last device solve.  Through scipy and PCIe (export, host operation, re-upload): `submatrix`, `T`, sums of matrices with different patterns, every other solver.'''
 
@@ -374,6 +377,16 @@ class HipMatrix:
         bound without having fallen in that cycle (or in the
         one after it, which may get a direction of the size of a rounding and no further) the solve raises MatrixError('fgmres: singular matrix').
 
+        solver='minres': MINRES of Paige and Saunders on the device for a SYMMETRIC matrix, definite or not, and ONE right-hand side, with the keywords, the row
+        mask, the stopping rule and the true-residual restart of 'cg'.  One product and three launches an iteration, a three-term recurrence on a fixed handful
+        of vectors.  `precon='diag'` is M^-1 = 1 / |A_ii| (MINRES needs a positive definite preconditioner; a zero on the diagonal of a free row is the
+        MatrixError of the others: a saddle point with a zero block takes `precon=None`); 'amg' and `preconargs` are refused.  With a preconditioner the
+        iteration minimises the residual in the M^-1-norm; the 2-norm residual that the bound is about is carried beside it.  The iteration stops itself on
+        the device, so `iterations` is exact whatever `check` is.  The only failures of the recurrence are a scalar that is not finite and a rotation that
+        vanishes (the zero matrix): after progress the recurrence restarts from the true residual, at the first step after a start that is
+        MatrixError('minres: breakdown').  The matrix is NOT checked for symmetry: on a nonsymmetric matrix the recurrence converges to something the true
+        residual rejects, the restarts get nowhere, and the solve ends in ToleranceNotReached, not in a wrong answer.
+
         Any other `solver` is a PCIe path: the matrix is exported to a ScipyMatrix and solved there.
 
         Returns a numpy vector, or a device tensor if `rhs` was one.'''
@@ -388,7 +401,7 @@ class HipMatrix:
                 raise MatrixError('right-hand side shape does not match matrix shape')
         if nrows != ncols:
             raise MatrixError(f'constrained matrix is not square: {nrows}x{ncols}')
-        if solver not in ('cg', 'bicgstab', 'fgmres'):
+        if solver not in ('cg', 'minres', 'bicgstab', 'fgmres'):
             x = self._scipy().solve(_host(rhs), lhs0=_host(lhs0), constrain=_host(constrain), **solverargs)
             if on_device:
                 from . import device
@@ -412,6 +425,8 @@ class HipMatrix:
             return self._cg(*args, preconargs)
         if solver == 'bicgstab':
             return self._bicgstab(*args)
+        if solver == 'minres':
+            return self._minres(*args)
         return self._fgmres(*args, int(restart))
 
     def solve_leniently(self, *args, **kwargs):
@@ -530,6 +545,45 @@ class HipMatrix:
                     break  # restart from where the recurrence got to
                 if not numpy.isfinite(rr):
                     raise MatrixError('bicgstab: non-finite residual')
+                if rr <= stop_rr:
+                    break
+
+    def _minres(self, rhs, free, lhs, atol, rtol, precon, maxiter, check, on_device):
+        from . import device, kernels
+        n = self.shape[0]
+        values, rowptr, colidx = self.triplet()
+        mask, x, b, dinv = self._krylov_setup(rhs, free, lhs, precon, on_device)
+        if dinv is not None:
+            dinv = dinv.abs()  # (the preconditioner of MINRES is positive definite: 1 / |diag|)
+        r, r1, r2, v, q, w1, w2 = (device.empty(n, 'float64') for _ in range(7))
+        work = kernels.minres_work()
+        result = (lambda: x) if on_device else (lambda: device.to_host(x))
+        stop_rr, it = None, 0
+        while True:  # a start: from the true residual
+            self.iterations = it
+            self.spmv(x, alpha=-1., beta=1., b=b, rowmask=mask, y=r)  # mask(rhs - A x)
+            kernels.minres_init(dinv, r, r1, r2, v, w1, w2, work)
+            rr = work[:1].item()
+            if stop_rr is None:
+                stop_rr = max(atol, rtol * rr ** .5) ** 2  # (the device compares r . r with this number, and so does the host)
+            if not numpy.isfinite(rr):
+                raise MatrixError('minres: non-finite residual')
+            if rr <= stop_rr:
+                return result()
+            if it >= maxiter:
+                raise ToleranceNotReached(result())
+            start = it
+            while it < maxiter:
+                kernels.minres_iterate(values, rowptr, colidx, self._ncols, rowmask=mask, dinv=dinv, x=x, r=r, r1=r1, r2=r2, v=v, q=q, w1=w1, w2=w2, work=work,
+                                       stop_rr=stop_rr, niter=min(check, maxiter - it), col32=self._columns(), lanes=self.lanes)
+                rr, flag, moved = work[:3].tolist()
+                self.iterations = it = start + int(moved)  # (the device counts the iterations that moved x: exact, not a multiple of `check`)
+                if flag:
+                    if not moved:
+                        raise MatrixError('minres: breakdown')
+                    break  # restart from where the recurrence got to
+                if not numpy.isfinite(rr):
+                    raise MatrixError('minres: non-finite residual')
                 if rr <= stop_rr:
                     break
 

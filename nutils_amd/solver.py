@@ -10,7 +10,7 @@ without line search); minimisation / pseudo-time drivers stay with the reference
 
 Under a matrix backend with a device hand-over (``assemble_device``: ``matrix.backend('hip')``)
 the merged Jacobian stays in HBM instead: it is a ``HipMatrix`` on the plan's index tensors,
-constraints are the row mask of its Krylov solve, and `linargs` (solver name -- 'cg', 'bicgstab' or
+constraints are the row mask of its Krylov solve, and `linargs` (solver name -- 'cg', 'minres', 'bicgstab' or
 'fgmres' run on the device --, tolerance, for 'fgmres' also `restart`) go to every linear solve.  Residual, iterate and arguments remain host vectors.'''
 
 import numpy
@@ -437,7 +437,7 @@ class System:
         every linear solve (solver.py:618-661): a linear system calls `jac.solve(res, **linargs)`, a Newton step `jac.solve_leniently(res, **linargs)` with
         rtol = 1e-3 unless `linargs` names a tolerance.  Under a matrix backend that takes device tensors (`matrix.backend('hip')`) the Jacobian stays in HBM
         and the constraints are the row mask of its solve; that solve is iterative, so `linargs` must name a `solver` ('cg' for symmetric positive definite
-        systems, 'bicgstab' or 'fgmres' for any square one) and a tolerance; `linear_iterations` then lists the iterations (for 'fgmres': Arnoldi steps) of every
+        systems, 'minres' for symmetric indefinite ones, 'bicgstab' or 'fgmres' for any square one) and a tolerance; `linear_iterations` then lists the iterations (for 'fgmres': Arnoldi steps) of every
         linear solve.'''
         x, free = self._pack(dict(arguments or {}), constrain)
         args = self._unpack(dict(arguments or {}), x)

@@ -14,6 +14,11 @@
     vectors four times), the product's share of it and the share of everything else (the Gram-Schmidt kernels, the scalar kernel, the normalisation), the
     model's bytes of that rest, (4 (j + 1) + c) 8 n per step with c = 2 ceil((j + 1) / 8) + 8 passes over w, z, dinv and the new basis vector, over its time as a
     fraction of 8 TB/s, and steps, wall time and true residual of a Jacobi-GMRES solve under the conditions of the BiCGStab solve,
+  * for the symmetric indefinite twin S (section 'minres'; the off-diagonal entries of K, the diagonal +-sum_j |K_ij| with the sign alternating from row to row:
+    by Gershgorin |lambda| >= K_ii, half of the spectrum negative), built on the device from the value tensor: the time of a MINRES iteration against one
+    product of the same run, and of a BiCGStab iteration and of a GMRES(30) step on the same matrix in the same process, their windows alternating; and
+    iterations, wall time and true residual of a solve to rtol = 1e-8 by each of the three, on S and on the Helmholtz-like twin K - 0.01 diag(K), whose
+    Jacobi-scaled spectrum crosses zero at its low end (the same pattern and kernels: the iteration times are those of S),
   * for the smoothed-aggregation AMG preconditioner (precon='amg'): the time of the symbolic and of the numeric phase of its setup, level sizes and operator
     complexity, one cycle against one masked product, and iterations, wall time and true residual of an AMG-CG solve (with the symbolic phase, and with it
     cached) beside the Jacobi-CG solve of the same system in the same process; for the vector matrices (elasticity96, p2vector32) all of that once more with
@@ -24,7 +29,7 @@
     each ratio, and with --eigsteps 5,10,20 for each number of Lanczos steps.
 
 Usage: python tools/matrix_probe.py [--matrices poisson128,elasticity96,elasticity64,elasticity48,bilinear2048,bilinear1024,p2vector32,p2vector16] [--scale 1.0]
-[--sections spmv,cg,bicgstab,fgmres,amg,smoother] [--eigratios 4,10,30] [--eigsteps 5,10,20] [--out FILE]
+[--sections spmv,cg,bicgstab,fgmres,minres,amg,smoother] [--eigratios 4,10,30] [--eigsteps 5,10,20] [--out FILE]
 (--scale shrinks every mesh for a quick look; --sections leaves parts out).  Not run by any test.'''
 import argparse
 import json
@@ -152,6 +157,8 @@ def probe(name, args):
         info['bicgstab'] = probe_bicgstab(A, free, mask, rhs_dev, res0, args)
     if 'fgmres' in args.sections:
         info['fgmres'] = probe_fgmres(A, free, mask, rhs_dev, res0, args)
+    if 'minres' in args.sections:
+        info['minres'] = probe_minres(A, free, mask, rhs_dev, res0, args)
     if 'amg' in args.sections:
         info['amg'] = probe_amg(A, free, mask, rhs_dev, res0, info, args)
     if 'smoother' in args.sections:
@@ -528,6 +535,120 @@ def probe_fgmres(A, free, mask, rhs_dev, res0, args):
     return out
 
 
+def indefinite_twin(A):
+    '''S: the off-diagonal entries of K, the diagonal +-sum_j |K_ij|, + on even rows and - on odd ones, on the index tensors of A (set-up, not timed).  Symmetric,
+    and by Gershgorin every eigenvalue is at least K_ii from zero, on the side of its row's sign.'''
+    import torch
+    values, rowptr, colidx = A.triplet()
+    n = A.shape[0]
+    rows = torch.repeat_interleave(torch.arange(n, device=values.device), rowptr[1:] - rowptr[:-1])
+    rowabs = torch.zeros(n, dtype=values.dtype, device=values.device).index_add_(0, rows, values.abs())
+    sign = 1. - 2. * (torch.arange(n, device=values.device) % 2)
+    return A._with_values(torch.where(colidx == rows, (sign * rowabs)[rows], values))
+
+
+def shifted_twin(A, sigma):
+    '''K - sigma diag(K) on the index tensors of A (set-up, not timed): the spectrum of the Jacobi-scaled matrix moved down by sigma, so that its low end is
+    negative and the rest is not, as in a Helmholtz problem; the diagonal keeps its sign, and Jacobi is the same preconditioner for every solver'''
+    import torch
+    values, rowptr, colidx = A.triplet()
+    rows = torch.repeat_interleave(torch.arange(A.shape[0], device=values.device), rowptr[1:] - rowptr[:-1])
+    return A._with_values(torch.where(colidx == rows, (1. - sigma) * values, values))
+
+
+MINRES_STEPS = 20
+SHIFT = .01
+
+
+def probe_minres(A, free, mask, rhs_dev, res0, args):
+    '''the symmetric indefinite twin of A: the time of a MINRES iteration beside a BiCGStab iteration and a GMRES(30) step, and a solve by each'''
+    import torch
+    from nutils_amd import device, kernels, matrix
+    _, rowptr, colidx = A.triplet()
+    nrows, ncols = A.shape
+    S = indefinite_twin(A)
+    svalues = S.triplet()[0]
+    csr = dict(rowmask=mask, col32=A._columns(), lanes=A.lanes)
+    dinv = (1. / S._diagonal_dev()).masked_fill(mask == 0, 0.)
+    dabs = dinv.abs()
+    r0 = torch.from_numpy(numpy.random.default_rng(1).normal(size=nrows) * free).cuda()
+    m = 30
+    vec = {name: torch.zeros_like(r0) for name in ('x', 'r', 'r1', 'r2', 'v', 'q', 'w1', 'w2', 'rhat', 'p', 's', 't', 'phat', 'shat', 'z', 'w')}
+    V = torch.zeros((m + 1) * nrows, dtype=torch.float64, device='cuda')
+    mwork, bwork, gwork = kernels.minres_work(), kernels.bicgstab_work(), kernels.gmres_work(m)
+
+    # the same state before every timed call: no iteration may converge or break down inside a window (the bound is zero)
+    def minres_start():
+        vec['x'].zero_()
+        vec['r'].copy_(r0)
+        kernels.minres_init(dabs, *(vec[name] for name in ('r', 'r1', 'r2', 'v', 'w1', 'w2')), mwork)
+
+    def minres_steps():
+        minres_start()
+        kernels.minres_iterate(svalues, rowptr, colidx, ncols, dinv=dabs, work=mwork, stop_rr=0., niter=MINRES_STEPS, **csr,
+                               **{name: vec[name] for name in ('x', 'r', 'r1', 'r2', 'v', 'q', 'w1', 'w2')})
+
+    def bicgstab_start():
+        vec['x'].zero_()
+        vec['r'].copy_(r0)
+        kernels.bicgstab_init(dinv, vec['r'], vec['rhat'], vec['p'], vec['phat'], bwork)
+
+    def bicgstab_steps():
+        bicgstab_start()
+        kernels.bicgstab_iterate(svalues, rowptr, colidx, ncols, dinv=dinv, work=bwork, stop_rr=0., niter=MINRES_STEPS, **csr,
+                                 **{name: vec[name] for name in ('x', 'r', 'rhat', 'p', 's', 't', 'phat', 'shat')}, v=vec['v'])
+
+    gmres_start = lambda: kernels.gmres_init(dinv, r0, V, vec['z'], gwork, restart=m)
+
+    def gmres_cycle():
+        gmres_start()
+        kernels.gmres_iterate(svalues, rowptr, colidx, ncols, dinv=dinv, V=V, z=vec['z'], w=vec['w'], work=gwork, restart=m, stop_rr=0., niter=m, **csr)
+
+    masked = lambda: S.spmv(vec['v'], y=vec['q'], rowmask=mask)
+    t = windows([minres_steps, minres_start, bicgstab_steps, bicgstab_start, gmres_cycle, gmres_start, masked], args.window)
+    out = dict(masked_spmv=stats(t[6]))
+    for name, steps, work, t_steps, t_start, n in (('minres', minres_steps, mwork, t[0], t[1], MINRES_STEPS), ('bicgstab', bicgstab_steps, bwork, t[2], t[3], MINRES_STEPS),
+                                                   ('fgmres30', gmres_cycle, gwork, t[4], t[5], m)):
+        steps()
+        _, flag, moved = work[:3].tolist()
+        out[name] = dict(moved_per_call=moved, flag=flag, iteration=stats([(a - b) / n for a, b in zip(t_steps, t_start)]))  # (n and 0, or the time is not that of an iteration)
+        out[name]['iteration_over_product'] = out[name]['iteration']['us'] / out['masked_spmv']['us']
+    # vector passes of 8 n bytes: lanczos q, r1, r2, dinv -> r1, r2 (6); update v, w1, w2, x, r, r2, dinv -> w1, w2, x, r, v (12)
+    out['minres']['vector_passes'] = 18
+    vector_us = out['minres']['iteration']['us'] - out['masked_spmv']['us']
+    out['minres']['vector_part_us'] = vector_us
+    out['minres']['vector_part_frac_6p3TBs'] = 18 * 8 * nrows / (vector_us * 1e-6) / 6.3e12 if vector_us > 0 else None
+    del vec, V
+    torch.cuda.empty_cache()
+
+    def solves(T, repeats):
+        '''a solve to rtol = 1e-8 by each of the three; the last of `repeats` is the timed one'''
+        results = {}
+        for name, kwargs in (('minres', dict(solver='minres')), ('bicgstab', dict(solver='bicgstab')), ('fgmres30', dict(solver='fgmres', restart=m))):
+            for _ in range(repeats):
+                device.synchronize()
+                t0 = time.perf_counter()
+                try:
+                    sol = T.solve(rhs_dev, constrain=~free, rtol=1e-8, maxiter=args.maxiter, **kwargs)
+                    res = dict(converged=True)
+                except matrix.ToleranceNotReached as e:
+                    sol = e.best
+                    res = dict(converged=False)
+                device.synchronize()
+                res.update(wall_ms=(time.perf_counter() - t0) * 1e3, iterations=T.iterations)
+            res['true_relative_residual'] = float(T.spmv(sol, alpha=-1., beta=1., b=rhs_dev, rowmask=mask).norm() / res0.norm())
+            res['ms_per_iteration'] = res['wall_ms'] / max(1, T.iterations)
+            results[name] = res
+            del sol
+        return results
+
+    for name, res in solves(S, 2).items():  # (the first solve warms every shape)
+        out[name]['solve'] = res
+    # the Helmholtz-like twin: the pattern and the kernels of S, so the iteration times above are its own; every shape is warm by now
+    out['shifted'] = dict(sigma=SHIFT, **solves(shifted_twin(A, SHIFT), 1))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--matrices', default='poisson128,elasticity96,bilinear2048,p2vector32')
@@ -535,7 +656,7 @@ def main():
     ap.add_argument('--window', type=float, default=.3)
     ap.add_argument('--maxiter', type=int, default=20000)
     ap.add_argument('--no-host-solve', action='store_true', help='skip the host BiCGStab of the nonsymmetric twin (minutes for the large matrices)')
-    ap.add_argument('--sections', default='spmv,cg,bicgstab,fgmres,amg', help='the parts of the probe to run')
+    ap.add_argument('--sections', default='spmv,cg,bicgstab,fgmres,minres,amg', help='the parts of the probe to run')
     ap.add_argument('--eigratios', default='', help="section 'smoother': the eigratio values of further Chebyshev degree-2 rows, e.g. 4,10,30")
     ap.add_argument('--eigsteps', default='', help="section 'smoother': the eigsteps values of further Chebyshev degree-2 rows, e.g. 5,10,20")
     ap.add_argument('--out', default=None)

@@ -11,10 +11,11 @@ and the lengths of what crossed PCIe towards the host during a warm step (device
 
 Workloads: `laplace` (the Laplace example, --laplace N elements per side, CG; also times solve_constraints), `elasticity96` (trilinear elasticity on 96^3
 elements, one face clamped and the opposite one displaced, CG), `cahnhilliard512` (one Newton step of the implicit Cahn-Hilliard step on 512^2 quadratic spline
-elements from a random state, Jacobi-BiCGStab).  The host route's direct solve is run up to --host-solve-dofs unknowns (3-D fill-in makes it a matter of hours
+elements from a random state, Jacobi-BiCGStab; --newton-solver names the device solver of that step, and a list such as bicgstab,minres reports the step
+once per solver, the first under `device`, the others under `device_<solver>`: the Jacobian is symmetric with a saddle).  The host route's direct solve is run up to --host-solve-dofs unknowns (3-D fill-in makes it a matter of hours
 and of hundreds of GB beyond); its assembly half is always run.
 
-Usage: python tools/system_probe.py [--workloads laplace,elasticity96,cahnhilliard512] [--scale 1.0] [--out FILE]
+Usage: python tools/system_probe.py [--workloads laplace,elasticity96,cahnhilliard512] [--scale 1.0] [--newton-solver bicgstab,minres] [--out FILE]
 (--scale shrinks every mesh for a quick look).  Not run by any test; no time in here is a pass criterion.'''
 import argparse
 import contextlib
@@ -200,7 +201,8 @@ def probe(name, args):
     elif name == 'cahnhilliard512':
         info['elements'] = [n(512)] * 2
         nrg, arguments = cahnhilliard(n(512))
-        linargs = dict(solver='bicgstab', rtol=args.newton_rtol, maxiter=args.maxiter)
+        solvers = args.newton_solver.split(',')
+        linargs = dict(solver=solvers[0], rtol=args.newton_rtol, maxiter=args.maxiter)
         make, constrain = (lambda: System(nrg, trial='φ,η')), None
     else:
         raise SystemExit(f'unknown workload {name!r}')
@@ -208,6 +210,9 @@ def probe(name, args):
     info['device'] = route(make, arguments, constrain, linargs, True, True, args.reps)
     if name == 'laplace':  # the same solve under the multigrid preconditioner: the first repetition builds the plan, the later ones reuse it (the median is theirs)
         info['device_amg'] = route(make, arguments, constrain, dict(linargs, precon='amg'), True, True, args.reps)
+    if name == 'cahnhilliard512':
+        for other in solvers[1:]:
+            info['device_' + other] = route(make, arguments, constrain, dict(linargs, solver=other), True, True, args.reps)
     info['host'] = route(make, arguments, constrain, linargs, False, info['device']['size'] <= args.host_solve_dofs, args.reps)
     return info
 
@@ -219,6 +224,7 @@ def main():
     ap.add_argument('--laplace', type=int, default=1024, help='elements per side of the Laplace example')
     ap.add_argument('--rtol', type=float, default=1e-8, help='relative tolerance of the linear workloads')
     ap.add_argument('--newton-rtol', type=float, default=1e-3, help="relative tolerance of the Newton step's linear solve (the default of System.solve)")
+    ap.add_argument('--newton-solver', default='bicgstab', help="device solver of the cahnhilliard512 step; a comma-separated list reports the step once per solver")
     ap.add_argument('--maxiter', type=int, default=20000)
     ap.add_argument('--reps', type=int, default=3)
     ap.add_argument('--host-solve-dofs', type=int, default=1200000, help="largest system the host route's direct solver is run on")
