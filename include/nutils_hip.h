@@ -703,6 +703,39 @@ int nh_csr_diagonal(const nh_csr *A, double *diag_dev, void *stream);
  * is no launch.  Column indices int32 or int64 as for the product, and its rows-to-lanes mapping.  Several lanes may store the byte 1 to one address: plain
  * byte stores, no atomics, and the result, a set, is the same at every call. */
 int nh_csr_support(const nh_csr *A, double tol, unsigned char *rowsupp_dev, unsigned char *colsupp_dev, void *stream);
+/* ---- matrix algebra on the device (nh_csr_ops.hip): Matrix.T, Matrix.submatrix and sums of different patterns (matrix/_base.py) ----
+ * Every operation returns index arrays and `pos`, the position in the operand of every entry of the result; the values are then
+ * nh_index_copy(nnz, values, pos, NULL, values_result), and a later matrix on the same pattern needs only that copy.  All outputs are pure
+ * functions of the inputs: repeated calls give identical arrays.  The rows of A hold their columns in ascending order (the triplet contract).
+ *
+ * nh_csr_transpose: the pattern of A^T.  rowptr_t_dev int64 [ncols + 1], colidx_t_dev and pos_dev int64 [nnz]; A->values_dev is not read and
+ * may be NULL, A->lanes is not used.  Rows of A^T come out sorted by column (the source row) and, where a row of A repeats a column, in the
+ * order of A.  pos is a permutation of 0 .. nnz - 1.  Phases: an int32 histogram of the columns (atomicAdd of ones; nrows <= INT32_MAX),
+ * nh_scan_exclusive, one slot of its output row claimed per entry (int32 atomicAdd), every output row sorted by its unique keys -- the two
+ * atomics cannot reach the result.  No floating point.  nnz is the caller's, so nothing is read back; the host waits only where
+ * nh_scan_exclusive does, and once more when ncols > 2 nnz (the histogram then has a buffer of its own instead of living in pos_dev).
+ * Output rows of up to 64 entries are sorted by one wave in registers, of 65 .. 2048 entries by a workgroup in LDS; a longer row takes a slow
+ * path that is quadratic in its length over 2048 (pieces of 2048 sorted in LDS, ranks by binary search in the other pieces).
+ *
+ * nh_csr_select_count / nh_csr_select_fill: compaction by a predicate.  Entry k of row i is kept iff rowkeep_dev[i] != 0, colkeep_dev[col[k]] != 0
+ * (uint8 [nrows] / [ncols]; NULL keeps all) and, if drop_zeros, values[k] != 0. (NaN is kept, -0. is not).  Kept rows and columns are numbered
+ * densely in ascending order; entries keep their order in a row.  `count` writes newrow_dev int64 [nrows + 1] and newcol_dev int64 [ncols + 1], the
+ * exclusive scans of the masks (NULL exactly where the mask is NULL), checks that the masks keep nrows_s rows and ncols_s columns -- what the
+ * caller sized its arrays for; NH_EINVAL otherwise, before anything is written through them -- writes rowptr_s_dev int64 [nrows_s + 1] and
+ * returns the number of kept entries in *nnz (host; synchronises the stream, the convention of nh_pattern_union_count).  `fill`, with the
+ * same arguments and the arrays `count` wrote, writes colidx_s_dev and pos_dev, int64 [*nnz].  Lanes per row as in the product (A->lanes);
+ * ranks within a row come from a wave vote per stride (__ballot, 64 bits).  No atomics.
+ *
+ * nh_csr_add_values: the values of a + sign b (sign 1. or -1.) on the union of two patterns, pos_a_dev / pos_b_dev being the positions of the
+ * parts' entries in the union (nh_pattern_union_fill): out = 0, out[pos_a[k]] = a[k], out[pos_b[k]] += sign b[k].  Positions are unique within a
+ * part: plain stores, no atomics.  out_dev double [nnz_u]. */
+int nh_csr_transpose(const nh_csr *A, int64_t *rowptr_t_dev, int64_t *colidx_t_dev, int64_t *pos_dev, void *stream);
+int nh_csr_select_count(const nh_csr *A, const unsigned char *rowkeep_dev, const unsigned char *colkeep_dev, int drop_zeros, int64_t nrows_s, int64_t ncols_s,
+                        int64_t *newrow_dev, int64_t *newcol_dev, int64_t *rowptr_s_dev, int64_t *nnz, void *stream);
+int nh_csr_select_fill(const nh_csr *A, const unsigned char *rowkeep_dev, const unsigned char *colkeep_dev, int drop_zeros, const int64_t *newrow_dev,
+                       const int64_t *newcol_dev, const int64_t *rowptr_s_dev, int64_t *colidx_s_dev, int64_t *pos_dev, void *stream);
+int nh_csr_add_values(int64_t nnz_a, const double *a_dev, const int64_t *pos_a_dev, int64_t nnz_b, const double *b_dev, const int64_t *pos_b_dev, double sign, int64_t nnz_u,
+                      double *out_dev, void *stream);
 /* Preconditioned conjugate gradients for square A, symmetric positive definite on the rows / columns the mask keeps, entirely on the
  * device: an iteration is three launches -- q = mask(A p) with partial sums of p . q per workgroup; alpha from the partials (summed by
  * every workgroup in the same order), x += alpha p, r -= alpha q, partials of r . z and r . r with z = dinv r; beta from those and

@@ -209,6 +209,10 @@ SIGNATURES = {
     'nh_csr_spmv': (ctypes.c_int, [ctypes.POINTER(Csr), ctypes.c_double, vp, ctypes.c_double, vp, vp, vp, vp]),
     'nh_csr_diagonal': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp]),
     'nh_csr_support': (ctypes.c_int, [ctypes.POINTER(Csr), ctypes.c_double, vp, vp, vp]),
+    'nh_csr_transpose': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, vp, vp]),
+    'nh_csr_select_count': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, ctypes.c_int, c_i64, c_i64, vp, vp, vp, c_i64p, vp]),
+    'nh_csr_select_fill': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
+    'nh_csr_add_values': (ctypes.c_int, [c_i64, vp, vp, c_i64, vp, vp, ctypes.c_double, c_i64, vp, vp]),
     'nh_cg_work_doubles': (c_i64, []),
     'nh_cg_init': (ctypes.c_int, [c_i64, vp, vp, vp, vp, vp]),
     'nh_cg_iterate': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, vp, vp, vp, vp, vp, ctypes.c_int, vp]),

@@ -860,6 +860,57 @@ def csr_support(values, rowptr, colidx, ncols, tol=0., *, rows=True, cols=True, 
     return rowsupp, colsupp
 
 
+def csr_transpose(rowptr, colidx, ncols, *, col32=None):
+    '''(rowptr_t, colidx_t, pos): the pattern of the transpose and the position in the operand of every entry of it (nh_csr_transpose); the values of the
+    transpose are `csr_gather(values, pos)`.  Rows sorted, the same tensors at every call.'''
+    nnz = colidx.numel()
+    rowptr_t, colidx_t, pos = device.empty(int(ncols) + 1, 'int64'), device.empty(nnz, 'int64'), device.empty(nnz, 'int64')
+    A = _lib.Csr(rowptr.numel() - 1, int(ncols), nnz, None, device.ptr(rowptr), device.ptr(colidx), device.ptr(col32), 0)
+    _lib.call('nh_csr_transpose', ctypes.byref(A), device.ptr(rowptr_t), device.ptr(colidx_t), device.ptr(pos), device.stream())
+    return rowptr_t, colidx_t, pos
+
+
+def csr_select(values, rowptr, colidx, ncols, *, rowkeep=None, colkeep=None, nrows_s=None, ncols_s=None, drop_zeros=False, col32=None, lanes=0, lazy=False):
+    '''(rowptr_s, colidx_s, pos): the entries of the rows that the uint8 device vector `rowkeep` keeps and of the columns that `colkeep` keeps (None: all),
+    without the exact zeros if `drop_zeros`; rows and columns numbered anew in ascending order, `pos` the position in the operand of every kept entry
+    (nh_csr_select_count, nh_csr_select_fill).  `nrows_s`, `ncols_s`: how many rows and columns the masks keep; the library checks them.  `lazy`: None
+    if every entry is kept and there are no masks -- the operand's own index tensors will do, the fill is skipped.'''
+    nrows = rowptr.numel() - 1
+    nrows_s = nrows if rowkeep is None else int(nrows_s)
+    ncols_s = int(ncols) if colkeep is None else int(ncols_s)
+    A = _csr(values, rowptr, colidx, ncols, col32, lanes)
+    newrow = None if rowkeep is None else device.empty(nrows + 1, 'int64')
+    newcol = None if colkeep is None else device.empty(int(ncols) + 1, 'int64')
+    rowptr_s = device.empty(nrows_s + 1, 'int64')
+    nnz = ctypes.c_int64()
+    masks = device.ptr(rowkeep), device.ptr(colkeep), int(bool(drop_zeros))
+    _lib.call('nh_csr_select_count', ctypes.byref(A), *masks, nrows_s, ncols_s, device.ptr(newrow), device.ptr(newcol), device.ptr(rowptr_s), ctypes.byref(nnz),
+              device.stream())
+    if lazy and rowkeep is None and colkeep is None and nnz.value == values.numel():
+        return None
+    colidx_s, pos = device.empty(nnz.value, 'int64'), device.empty(nnz.value, 'int64')
+    if nnz.value:
+        _lib.call('nh_csr_select_fill', ctypes.byref(A), *masks, device.ptr(newrow), device.ptr(newcol), device.ptr(rowptr_s), device.ptr(colidx_s), device.ptr(pos),
+                  device.stream())
+    return rowptr_s, colidx_s, pos
+
+
+def csr_gather(values, pos):
+    '''values[pos] as a new device vector (nh_index_copy): the values of a transpose or a selection from its plan'''
+    out = device.empty(pos.numel(), 'float64')
+    index_copy(values, out, src_index=pos)
+    return out
+
+
+def csr_add(a, pos_a, b, pos_b, sign, nnz_u):
+    '''the values of a + sign b on the union of two patterns, `pos_a` and `pos_b` the positions of the parts' entries in it (`pattern_union`): zero, a
+    placed, sign b added (nh_csr_add_values); sign is 1 or -1'''
+    out = device.empty(nnz_u, 'float64')
+    _lib.call('nh_csr_add_values', a.numel(), device.ptr(a), device.ptr(pos_a), b.numel(), device.ptr(b), device.ptr(pos_b), float(sign), int(nnz_u), device.ptr(out),
+              device.stream())
+    return out
+
+
 def cg_work():
     '''the work array of a CG solve (nh_cg_work_doubles): [0] = r . r of the recurrence, [1] = breakdown flag, [2] = the bound of `cg_stop`'''
     return device.empty(_lib.load().nh_cg_work_doubles(), 'float64')

@@ -14,13 +14,16 @@ positive definite systems, MINRES ('minres') for symmetric indefinite ones,
 BiCGStab ('bicgstab') and restarted GMRES ('fgmres') for any square matrix --
 run on the device (nh_csr.hip); ``function.eval(function.as_matrix(K))`` builds
 one without the triplet ever visiting the host, and so does ``solver.System``
-under this backend (``assemble_device``).  What a ``HipMatrix`` does
-through scipy and a re-upload -- ``submatrix``, ``T``, every solver other than
-'cg', 'minres', 'bicgstab' and 'fgmres', sums of matrices with different patterns -- says so in its
-docstring.
+under this backend (``assemble_device``).  The matrix algebra runs there too
+(nh_csr_ops.hip): ``T``, ``submatrix`` by masks or strictly increasing indices,
+and sums of matrices with different patterns.  What a ``HipMatrix`` does
+through scipy and a re-upload -- every solver other than 'cg', 'minres',
+'bicgstab' and 'fgmres', ``export``, ``submatrix`` by unordered or repeated
+integer indices -- says so in its docstring.
 '''
 
 import contextlib
+import weakref
 import numpy
 
 
@@ -161,6 +164,48 @@ def _host(a):
     return device.to_host(a)
 
 
+def _selector(sel, n, what):
+    '''A selector of `submatrix` as a bool mask of length n: a bool array, or integers that rise strictly (numeric.asboolean of the reference, numeric.py:494).
+    None for any other integer array in range (unordered, repeated, negative indices): those keep the host path.  Raises MatrixError for a wrong length, an
+    index out of range, more than one axis or a dtype that is neither bool nor integer.  Host arrays only: nothing is uploaded here.'''
+    sel = numpy.asarray(sel)
+    if sel.ndim != 1:
+        raise MatrixError(f'{what} selection must be a vector, got {sel.ndim} axes')
+    if sel.dtype == bool:
+        if len(sel) != n:
+            raise MatrixError(f'{what} mask has length {len(sel)}, expected {n}')
+        return sel
+    if not sel.size:
+        return numpy.zeros(n, dtype=bool)
+    if sel.dtype.kind not in 'iu':
+        raise MatrixError(f'{what} selection must be a bool mask or an integer array, got {sel.dtype}')
+    if int(sel.max()) >= n or int(sel.min()) < -n:
+        raise MatrixError(f'{what} index out of range for {n} {what}s')
+    if int(sel.min()) < 0 or (sel.size > 1 and not (sel[1:] > sel[:-1]).all()):
+        return None
+    mask = numpy.zeros(n, dtype=bool)
+    mask[sel] = True
+    return mask
+
+
+class _Plan:
+    '''The index side of a transpose or a submatrix: the result's (rowptr, colidx), its column count, and `pos`, where each of its entries lies in the operand.
+    `apply(values)` is the matrix for the operand's current values: one gather.  The plan remembers the last matrix it made, weakly: while that one lives the
+    next is made from it by `_with_values`, so its int32 columns, its AMG symbolic phase and its own plans carry over in turn.'''
+
+    def __init__(self, key, rowptr, colidx, pos, ncols):
+        self.key, self.rowptr, self.colidx, self.pos, self.ncols = key, rowptr, colidx, pos, ncols
+        self._last = None
+
+    def apply(self, values):
+        from . import kernels
+        values = kernels.csr_gather(values, self.pos)
+        last = self._last and self._last()
+        new = HipMatrix(values, self.rowptr, self.colidx, self.ncols) if last is None else last._with_values(values)
+        self._last = weakref.ref(new)
+        return new
+
+
 class HipMatrix:
     '''CSR matrix that lives in HBM, with the interface of the reference's Matrix (matrix/_base.py): `shape`, `size`, `@`, `diagonal`, `export`, scalar
     multiples, sums, `submatrix`, `T`, `solve`, `solve_leniently`.
@@ -169,12 +214,16 @@ class HipMatrix:
     first use on the device.  The matrix keeps references and never writes into them.  At the first product the column indices are narrowed to int32 once
     (12 instead of 16 bytes per entry; matrices with more than 2^31 - 1 columns keep the int64 indices).
 
-    On the device: products (nh_csr_spmv), the diagonal, `rowsupp` / `colsupp` (nh_csr_support), scalar multiples, sums of matrices that share their index tensors, `solve(solver='cg')`, a
+    On the device: products (nh_csr_spmv), the diagonal, `rowsupp` / `colsupp` (nh_csr_support), scalar multiples, sums (of matrices that share their index tensors: values only, zeros kept; of different
+    patterns: the union by nh_pattern_union_*, the values by nh_csr_add_values, the entries that cancel exactly dropped as scipy drops them, by nh_csr_select_*), `T`
+    (nh_csr_transpose) and `submatrix` by bool masks or strictly increasing indices (nh_csr_select_*) -- the index side of a transpose or a submatrix is a plan kept on
+    the matrix and handed on by `_with_values`, so the next matrix on the same pattern pays one gather (nh_index_copy) -- `solve(solver='cg')`, a
     conjugate-gradient iteration for SYMMETRIC POSITIVE DEFINITE systems preconditioned by Jacobi or by a smoothed-aggregation multigrid cycle (`precon='amg'`, amg.py), for SYMMETRIC systems that are indefinite (saddle points, Helmholtz) `solve(solver='minres')`, a MINRES iteration
     preconditioned by 1 / |diag|: one product a step, a residual that never rises in the norm it minimises, no breakdown short of the exhausted Krylov space;
     and for ANY square system (nonsymmetric, indefinite)
     `solve(solver='bicgstab')`, a Jacobi-preconditioned BiCGStab iteration, and `solve(solver='fgmres')`, Jacobi-preconditioned restarted GMRES, whose residual
-    norm never rises within a cycle; all with ONE right-hand side.  `iterations` is the iteration count of the last device solve.  Through scipy and PCIe (export, host operation, re-upload): `submatrix`, `T`, sums of matrices with different patterns, every other solver.'''
+    norm never rises within a cycle; all with ONE right-hand side.  `iterations` is the iteration count of the last device solve.  Through scipy and PCIe (export, host operation, re-upload): every other solver, `submatrix` by
+    integer indices that are not strictly increasing, and the algebra of a matrix made from host arrays in which a row repeats a column.'''
 
     def __init__(self, values, rowptr, colidx, ncols, *, validate=True):
         self._ncols = int(ncols)
@@ -195,7 +244,10 @@ class HipMatrix:
         self.cg_iterations = None
         self.iterations = None
         self._col32 = None
+        self._canonical = True if self._hostcsr is None else None  # (`_unique`: None until a host triplet has been looked at)
         self._amg = None  # (free mask, coarse, k, levels) of the last 'amg' setup: the symbolic phase, reused while pattern and mask stay
+        self._tplan = None  # the index side of `T` (_Plan), made at the first transpose
+        self._subplan = None  # the index side of the last `submatrix` (_Plan; its key: the two masks)
 
     @property
     def size(self):
@@ -219,12 +271,27 @@ class HipMatrix:
         return self._col32
 
     def _with_values(self, values):
-        '''a matrix on the same index tensors (and their int32 copy, and the symbolic phase of an 'amg' preconditioner with the mask it was made for)'''
+        '''a matrix on the same index tensors (and their int32 copy, the symbolic phase of an 'amg' preconditioner with the mask it was made for, and the plans of
+        its transpose and of its last submatrix)'''
         _, rowptr, colidx = self.triplet()
         new = HipMatrix(values, rowptr, colidx, self._ncols)
         new._col32 = self._col32
+        new._canonical = self._unique()
         new._amg = self._amg
+        new._tplan = self._tplan
+        new._subplan = self._subplan
         return new
+
+    def _unique(self):
+        '''whether no row repeats a column, which the algebra on the device takes for granted.  True of what the assembly leaves in HBM; host arrays, whose
+        validation lets equal neighbours pass as the reference's does, are looked at once.'''
+        if self._canonical is None:
+            self._canonical = True
+            if self._hostcsr is not None:
+                _, rowptr, colidx = self._hostcsr
+                same = numpy.flatnonzero(colidx[1:] == colidx[:-1]) + 1  # allowed only where a new row starts
+                self._canonical = not (same.size and not numpy.isin(same, rowptr).all())
+        return self._canonical
 
     def spmv(self, x, *, alpha=1., beta=0., b=None, rowmask=None, y=None, lanes=None):
         '''y = mask(alpha A x + beta b) on device tensors (nh_csr_spmv); `b` may be `y`'''
@@ -300,14 +367,53 @@ class HipMatrix:
         core.sort_indices()
         return HipMatrix(core.data, core.indptr.astype(numpy.int64), core.indices.astype(numpy.int64), core.shape[1])
 
-    def submatrix(self, rows, cols):
-        '''PCIe path: selected on the host by scipy and uploaded again.  A constrained `solve(solver='cg')` does not come here: it masks rows instead.'''
+    def _submatrix_host(self, rows, cols):
+        '''PCIe path: selected on the host by scipy and uploaded again'''
         return self._from_scipy(self._scipy().submatrix(rows, cols).core)
+
+    def _transpose_host(self):
+        '''PCIe path: transposed on the host by scipy and uploaded again'''
+        return self._from_scipy(self._scipy().core.T)
+
+    def _add_host(self, other, sign):
+        '''PCIe path: different patterns are merged on the host by scipy and the sum is uploaded'''
+        return self._from_scipy(self._scipy().core + sign * other._scipy().core)
+
+    # -- algebra: new index tensors, made on the device (nh_csr_ops.hip)
+
+    def submatrix(self, rows, cols):
+        '''The rows and columns selected by bool masks or by strictly increasing integer arrays (Matrix.submatrix with the reference's numeric.asboolean), made
+        on the device (nh_csr_select_*); stored zeros stay.  The selectors are checked on the host before anything is uploaded: a wrong length, an index out of
+        range or a dtype that is neither bool nor integer is a MatrixError.  All rows and all columns: the matrix itself.  The index side is kept (`_subplan`,
+        one entry, keyed by the two masks), so the same selection of the next matrix on these index tensors is one gather.  Integer arrays that are not strictly
+        increasing (unordered, repeated, negative) take the PCIe path: selected on the host by scipy and uploaded again.  A constrained `solve(solver='cg')` does
+        not come here: it masks rows instead.'''
+        rmask, cmask = _selector(rows, self.shape[0], 'row'), _selector(cols, self.shape[1], 'column')
+        if rmask is not None and cmask is not None and rmask.all() and cmask.all():
+            return self
+        if rmask is None or cmask is None or not self._unique():
+            return self._submatrix_host(rows, cols)
+        plan = self._subplan
+        if plan is None or not (numpy.array_equal(plan.key[0], rmask) and numpy.array_equal(plan.key[1], cmask)):
+            from . import device, kernels
+            values, rowptr, colidx = self.triplet()
+            rowptr_s, colidx_s, pos = kernels.csr_select(values, rowptr, colidx, self._ncols, rowkeep=None if rmask.all() else device.to_dev(rmask, 'uint8'),
+                                                         colkeep=None if cmask.all() else device.to_dev(cmask, 'uint8'), nrows_s=int(rmask.sum()),
+                                                         ncols_s=int(cmask.sum()), col32=self._col32, lanes=self.lanes)
+            plan = self._subplan = _Plan((rmask.copy(), cmask.copy()), rowptr_s, colidx_s, pos, int(cmask.sum()))
+        return plan.apply(self.triplet()[0])
 
     @property
     def T(self):
-        '''PCIe path: transposed on the host by scipy and uploaded again'''
-        return self._from_scipy(self._scipy().core.T)
+        '''the transpose, made on the device (nh_csr_transpose); the index side is kept (`_tplan`), so the transpose of the next matrix on these index tensors is
+        one gather'''
+        if not self._unique():
+            return self._transpose_host()
+        if self._tplan is None:
+            from . import kernels
+            _, rowptr, colidx = self.triplet()
+            self._tplan = _Plan(None, *kernels.csr_transpose(rowptr, colidx, self._ncols, col32=self._col32), self.shape[0])
+        return self._tplan.apply(self.triplet()[0])
 
     # -- algebra: new values, shared indices
 
@@ -332,8 +438,18 @@ class HipMatrix:
         a, b = self.triplet(), other.triplet()
         if a[1] is b[1] and a[2] is b[2]:  # one pattern (scalar multiples, re-assemblies on the plan's index tensors): values only, on the device
             return self._with_values(a[0] + b[0] if sign > 0 else a[0] - b[0])
-        core = self._scipy().core + sign * other._scipy().core  # PCIe path: different patterns are merged on the host
-        return self._from_scipy(core)
+        if not (self._unique() and other._unique()):
+            return self._add_host(other, sign)
+        # different patterns: their union (nh_pattern_union_*), the values a + sign b written into it (nh_csr_add_values), and the entries that cancelled exactly
+        # dropped as scipy's sparse sum drops them (nh_csr_select_*; NaN stays).  No plan: the pattern of a sum depends on the values.
+        from . import kernels
+        rowptr, colidx, (pa, pb) = kernels.pattern_union([a[1:], b[1:]])
+        values = kernels.csr_add(a[0], pa, b[0], pb, sign, colidx.numel())
+        pruned = kernels.csr_select(values, rowptr, colidx, self._ncols, drop_zeros=True, lanes=spmv_lanes(self.shape[0], colidx.numel()), lazy=True)
+        if pruned is not None:  # (None: nothing cancelled, the union is the result)
+            rowptr, colidx, pos = pruned
+            values = kernels.csr_gather(values, pos)
+        return HipMatrix(values, rowptr, colidx, self._ncols)
 
     def __sub__(self, other):
         return self.__add__(other, sign=-1.)

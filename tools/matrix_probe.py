@@ -26,10 +26,16 @@
   * for the smoothers of that preconditioner (section 'smoother'; the rigid-body modes for the vector matrices), in one process and alternating: Jacobi with one
     (the default) and two sweeps and Chebyshev of degree 2 and 3 -- the numeric setup with the share of its Lanczos estimates, the bounds of every level, one
     cycle, and iterations and wall time of the solve to rtol = 1e-8 with the symbolic phase cached; with --eigratios 4,10,30 the Chebyshev degree-2 solve for
-    each ratio, and with --eigsteps 5,10,20 for each number of Lanczos steps.
+    each ratio, and with --eigsteps 5,10,20 for each number of Lanczos steps,
+  * for the matrix algebra (section 'algebra'; nh_csr_ops.hip): the wall time of `T`, of `submatrix(free, free)` and of two sums of different patterns (K + D, D
+    the diagonal as a matrix of its own, a shifted operator; K + K^T on the tensors of the transpose, the same pattern met again) -- first, on a matrix without
+    plans (the median of five after a warm-up, the device synchronised: these calls wait for the host), and with the plan (HIP events over windows, as the
+    product) -- beside the host path of the same matrix in the same process (`_transpose_host`, `_submatrix_host`, `_add_host` on a matrix without a host
+    copy, so the export is in it, as it was before; timed once, it takes seconds), with the bytes each device operation has to move and what fraction of
+    8 TB/s that is.
 
 Usage: python tools/matrix_probe.py [--matrices poisson128,elasticity96,elasticity64,elasticity48,bilinear2048,bilinear1024,p2vector32,p2vector16] [--scale 1.0]
-[--sections spmv,cg,bicgstab,fgmres,minres,amg,smoother] [--eigratios 4,10,30] [--eigsteps 5,10,20] [--out FILE]
+[--sections spmv,cg,bicgstab,fgmres,minres,amg,smoother,algebra] [--eigratios 4,10,30] [--eigsteps 5,10,20] [--out FILE]
 (--scale shrinks every mesh for a quick look; --sections leaves parts out).  Not run by any test.'''
 import argparse
 import json
@@ -163,6 +169,8 @@ def probe(name, args):
         info['amg'] = probe_amg(A, free, mask, rhs_dev, res0, info, args)
     if 'smoother' in args.sections:
         info['smoother'] = probe_smoother(A, free, mask, rhs_dev, res0, info, args)
+    if 'algebra' in args.sections:
+        info['algebra'] = probe_algebra(A, free, args)
     return info
 
 
@@ -204,6 +212,73 @@ def probe_spmv(A, x, y, nbytes, torch_fn, info, args):
         S @ xh
     info['scipy_matvec_ms'] = (time.perf_counter() - t0) / 3 * 1e3
     del S, hv, hrp, hci
+
+
+def probe_algebra(A, free, args):
+    '''T, submatrix(free, free) and sums of different patterns: first, with the plan, and on the host path'''
+    import torch
+    from nutils_amd import device, matrix
+    values, rowptr, colidx = A.triplet()
+    nrows, ncols = A.shape
+    nnz = A.nnz
+    idx = 4 if A._col32 is not None else 8  # bytes of a column index as the kernels read it
+
+    def plain():  # the matrix without plans and without a host copy
+        B = matrix.HipMatrix(values, rowptr, colidx, ncols)
+        B._col32 = A._col32
+        return B
+
+    def wall(fn, repeats=5):
+        fn()
+        times = []
+        for _ in range(repeats):
+            device.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            device.synchronize()
+            times.append(time.perf_counter() - t0)
+        return dict(ms=float(numpy.median(times)) * 1e3, spread=float((max(times) - min(times)) / numpy.median(times)))
+
+    def once(fn):
+        device.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        device.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    def with_bytes(entry, nbytes):
+        entry.update(bytes=int(nbytes), frac_8TBs=nbytes / (entry.get('ms', entry.get('us', 0) * 1e-3) * 1e-3) / 8e12)
+        return entry
+
+    out = {}
+    gather = lambda n: 24 * n  # pos, the value it points at, the value written
+    # transpose: the histogram reads the columns, the placement reads them again and writes a key, the sort reads the key and writes pos and the source row
+    planned = plain()
+    T = planned.T
+    out['T'] = dict(first=with_bytes(wall(lambda: plain().T), nnz * (2 * idx + 8 + 24) + 24 * ncols + gather(nnz)),
+                    plan=with_bytes(stats(windows([lambda: planned.T], args.window)[0]), gather(nnz)),
+                    host_ms=once(lambda: plain()._transpose_host()))
+    # submatrix: count and fill read the columns (and the mask bytes they point at), the fill writes a column and a position per kept entry
+    S = planned.submatrix(free, free)
+    out['submatrix'] = dict(kept=S.nnz, first=with_bytes(wall(lambda: plain().submatrix(free, free)), nnz * 2 * idx + 32 * nrows + 16 * S.nnz + gather(S.nnz)),
+                            plan=with_bytes(stats(windows([lambda: planned.submatrix(free, free)], args.window)[0]), gather(S.nnz)),
+                            host_ms=once(lambda: plain()._submatrix_host(free, free)))
+    # sums: the union reads both column lists twice and writes the union and both position lists; the values are zeroed, placed and added; the pruning pass
+    # counts over columns and values and, where something cancelled (the stored zeros of an assembled matrix do, as on the host), fills and gathers
+    from nutils_amd import kernels
+    n = min(nrows, ncols)
+    D = matrix.HipMatrix(torch.full((n,), .5, dtype=torch.float64, device='cuda'), torch.arange(nrows + 1, device='cuda').clamp(max=n), torch.arange(n, device='cuda'), ncols)
+    for key, B in (('K+D', D), ('K+KT', T)):
+        if B.shape != A.shape:
+            continue
+        union = kernels.pattern_union([A.triplet()[1:], B.triplet()[1:]])[1].numel()
+        kept = (plain() + B).nnz
+        nbytes = 2 * 8 * (nnz + B.nnz) + 8 * union + 8 * (nnz + B.nnz) + 8 * union + 24 * nnz + 32 * B.nnz + 16 * union + 32 * nrows
+        if kept < union:
+            nbytes += 16 * union + 16 * kept + gather(kept)
+        out[key] = dict(nnz_other=B.nnz, nnz_union=union, nnz_sum=kept, first=with_bytes(wall(lambda: plain() + B), nbytes),
+                        host_ms=once(lambda: plain()._add_host(matrix.HipMatrix(*B.triplet(), ncols), 1.)))
+    return out
 
 
 def probe_cg(A, free, mask, rhs_dev, res0, info, args):
