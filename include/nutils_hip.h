@@ -752,6 +752,34 @@ int64_t nh_cg_work_doubles(void);
 int nh_cg_init(int64_t n, const double *dinv_dev, const double *r_dev, double *p_dev, double *work_dev, void *stream);
 int nh_cg_iterate(const nh_csr *A, const unsigned char *rowmask_dev, const double *dinv_dev, double *x_dev, double *r_dev, double *p_dev, double *q_dev,
                   double *work_dev, int niter, void *stream);
+/* ---- several vectors at once (nh_csr_multi.hip): the product with a block of vectors, a batched CG ----
+ * A block of vectors is row-major [n][k] with a leading dimension ld >= k in doubles: numpy's C order of an (n, k) array, a column slice of a wider block
+ * being a view (its pointer and the wider block's ld).
+ * nh_csr_spmm: Y = mask(alpha A X + beta B) for any k >= 1, by the rules of nh_csr_spmv (b_dev may be NULL and may be y_dev, x_dev must not overlap y_dev,
+ * masked rows get zeros and their entries are not read, nothing atomic, repeated calls bit-identical).  Every (value, column) pair of the matrix is read once
+ * per group of NH_MULTI_MAX columns and used for each of them; a remnant group neither reads nor writes past column k.  Rows of X are read two doubles at
+ * a time where ldx is even and x_dev lies on a 16-byte boundary.  For every column the sums are formed in the order of nh_csr_spmv: column j of Y is, bit
+ * for bit, the single-vector product of column j at the same lanes and index width.  nnz == 0 without b_dev zero-fills the k columns of every row (ldy
+ * respected) without a launch.
+ * nh_cgm_*: k <= NH_MULTI_MAX independent conjugate-gradient recurrences on one matrix, Jacobi-preconditioned (dinv_dev) or plain (NULL), by the rules of
+ * nh_cg_* per column; x, r, p, q are blocks with ld = k, dinv and the row mask are shared.  An iteration is three launches that cover all columns: Q =
+ * mask(A P) with the partials of p_j . q_j, the update, the direction.  work_dev: nh_cgm_work_doubles(k) doubles (-1 and an error for a k out of range).  The
+ * head of the work array is the caller's:
+ *   work[0 .. k)      r . r of each recurrence                                 (read)
+ *   work[k .. 2k)     breakdown flags, 0. / 1.                                 (read)
+ *   work[2k .. 3k)    iterations since nh_cgm_init that moved the column       (read; exact, whatever niter was)
+ *   work[3k .. 4k)    the bounds on r . r, cleared by nh_cgm_init              (written by the caller after nh_cgm_init)
+ * so one copy of 3k doubles tells the host where every column stands.  A column with r . r <= its bound idles as nh_cg_iterate does: no arithmetic, no flag,
+ * p . q = 0 is no breakdown; a flagged column does no arithmetic on x, r, p either.  Idle columns still take part in the product: their p does not move, so
+ * their q does not.  Column j of x, r, p after any number of iterations is, bit for bit, what nh_cg_* make of column j alone with the same bound.
+ * Argument errors are NH_EINVAL (k < 1, ld < k, NULL vectors, a matrix that is not square, a negative niter) or NH_ELIMIT (k > NH_MULTI_MAX in nh_cgm_*). */
+#define NH_MULTI_MAX 8
+int nh_csr_spmm(const nh_csr *A, int k, double alpha, const double *x_dev, int64_t ldx, double beta, const double *b_dev, int64_t ldb,
+                const unsigned char *rowmask_dev, double *y_dev, int64_t ldy, void *stream);
+int64_t nh_cgm_work_doubles(int k);
+int nh_cgm_init(int64_t n, int k, const double *dinv_dev, const double *r_dev, double *p_dev, double *work_dev, void *stream);
+int nh_cgm_iterate(const nh_csr *A, int k, const unsigned char *rowmask_dev, const double *dinv_dev, double *x_dev, double *r_dev, double *p_dev, double *q_dev,
+                   double *work_dev, int niter, void *stream);
 /* Right-preconditioned BiCGStab for ANY square A (nonsymmetric, indefinite), M^-1 = dinv (Jacobi) or the identity (dinv_dev NULL), entirely on the
  * device and by the rules of the CG above: constraints are a row mask on which every vector vanishes, nothing is atomic, no scalar visits the host,
  * repeated solves are bit-identical.  An iteration is five launches: v = mask(A phat) with partial sums of rhat . v; alpha = rho / rhat . v, s = r - alpha v,

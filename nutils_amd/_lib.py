@@ -216,6 +216,10 @@ SIGNATURES = {
     'nh_cg_work_doubles': (c_i64, []),
     'nh_cg_init': (ctypes.c_int, [c_i64, vp, vp, vp, vp, vp]),
     'nh_cg_iterate': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, vp, vp, vp, vp, vp, ctypes.c_int, vp]),
+    'nh_csr_spmm': (ctypes.c_int, [ctypes.POINTER(Csr), ctypes.c_int, ctypes.c_double, vp, c_i64, ctypes.c_double, vp, c_i64, vp, vp, c_i64, vp]),
+    'nh_cgm_work_doubles': (c_i64, [ctypes.c_int]),
+    'nh_cgm_init': (ctypes.c_int, [c_i64, ctypes.c_int, vp, vp, vp, vp, vp]),
+    'nh_cgm_iterate': (ctypes.c_int, [ctypes.POINTER(Csr), ctypes.c_int, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int, vp]),
     'nh_bicgstab_work_doubles': (c_i64, []),
     'nh_csr_spmv_dots': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, vp, vp, vp, vp]),
     'nh_bicgstab_init': (ctypes.c_int, [c_i64, vp, vp, vp, vp, vp, vp, vp]),

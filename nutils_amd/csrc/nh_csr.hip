@@ -666,22 +666,6 @@ __device__ __forceinline__ void st(double *p, const Pack<VW> &a) {
     *p = a.v[0];
 }
 
-// block_sum of C numbers at once
-template <int C>
-__device__ __forceinline__ void block_sum_n(double (&s)[C], double *lds) {
-#pragma unroll
-  for (int c = 0; c < C; ++c)
-#pragma unroll
-    for (int o = 32; o; o >>= 1) s[c] += __shfl_xor(s[c], o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int c = 0; c < C; ++c) lds[4 * c + (threadIdx.x >> 6)] = s[c];
-  __syncthreads();
-#pragma unroll
-  for (int c = 0; c < C; ++c) s[c] = ((lds[4 * c] + lds[4 * c + 1]) + lds[4 * c + 2]) + lds[4 * c + 3];
-}
-
 // the column the step works on: G_COUNT, kept inside the basis whatever the cell holds
 __device__ __forceinline__ int gmres_column(const double *work, int m) { return max(0, min((int)work[G_COUNT], m - 1)); }
 

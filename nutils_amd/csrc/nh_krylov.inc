@@ -1,4 +1,4 @@
-// What the Krylov solvers of nh_csr.hip and nh_amg.hip share, so that the two files cannot drift apart: the workgroup size and grid caps, the sums over a
+// What the Krylov solvers of nh_csr.hip, nh_csr_multi.hip and nh_amg.hip share, so that the files cannot drift apart: the workgroup size and grid caps, the sums over a
 // workgroup and over the partials of the kernel before, the checks of a CSR view, and the head of a CG work array.  Included inside the anonymous namespace of
 // each file.
 
@@ -17,6 +17,22 @@ __device__ __forceinline__ double block_sum(double s, double *lds) {
   if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
   __syncthreads();
   return ((lds[0] + lds[1]) + lds[2]) + lds[3];
+}
+
+// block_sum of C numbers at once (lds: 4 C doubles), each added in block_sum's order
+template <int C>
+__device__ __forceinline__ void block_sum_n(double (&s)[C], double *lds) {
+#pragma unroll
+  for (int c = 0; c < C; ++c)
+#pragma unroll
+    for (int o = 32; o; o >>= 1) s[c] += __shfl_xor(s[c], o, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int c = 0; c < C; ++c) lds[4 * c + (threadIdx.x >> 6)] = s[c];
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < C; ++c) s[c] = ((lds[4 * c] + lds[4 * c + 1]) + lds[4 * c + 2]) + lds[4 * c + 3];
 }
 
 // sum of n partials, the same order in every workgroup

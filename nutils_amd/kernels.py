@@ -932,6 +932,71 @@ def cg_iterate(values, rowptr, colidx, ncols, *, rowmask, dinv, x, r, p, q, work
               device.ptr(p), device.ptr(q), device.ptr(work), int(niter), device.stream())
 
 
+MULTI_MAX = 8  # NH_MULTI_MAX: columns per group of the block product, and the most a batched CG takes at once
+
+
+def _block(name, t, nrows):
+    '''(k, ld) of a block of vectors: a 2-D float64 device tensor of `nrows` rows with unit column stride; its row stride is the leading dimension'''
+    if not (hasattr(t, 'data_ptr') and t.is_cuda and t.dtype == device.torch().float64 and t.dim() == 2):
+        raise ValueError(f'{name} must be a 2-D float64 device tensor')
+    n, k = t.shape
+    if n != nrows or k < 1:
+        raise ValueError(f'{name} has shape {tuple(t.shape)}, expected ({nrows}, k) with k >= 1')
+    if t.stride(1) != 1:
+        raise ValueError(f'{name} must have unit column stride (got strides {tuple(t.stride())}): a block of vectors is row-major')
+    if n > 1 and t.stride(0) < k:
+        raise ValueError(f'{name} has row stride {t.stride(0)} for {k} columns: rows must not overlap')
+    return k, (t.stride(0) if n > 1 else k)
+
+
+def csr_spmm(values, rowptr, colidx, ncols, X, *, Y=None, alpha=1., beta=0., B=None, rowmask=None, col32=None, lanes=0):
+    '''Y = mask(alpha A X + beta B) for a block of k >= 1 vectors (nh_csr_spmm): the matrix is read once per group of `MULTI_MAX` columns.  `X` (ncols, k), `B`
+    and `Y` (nrows, k) are 2-D float64 device tensors with unit column stride and any row stride (a column slice of a wider tensor is fine); anything else
+    is a ValueError.  `B` may be `Y`.  Column j of the result is, bit for bit, `csr_spmv` of column j.'''
+    nrows = rowptr.numel() - 1
+    k, ldx = _block('X', X, int(ncols))
+    if Y is None:
+        Y = device.torch().empty((nrows, k), dtype=X.dtype, device=X.device)
+    ky, ldy = _block('Y', Y, nrows)
+    kb, ldb = (k, 0) if B is None else _block('B', B, nrows)
+    if ky != k or kb != k:
+        raise ValueError(f'X has {k} columns, Y {ky}' + ('' if B is None else f', B {kb}'))
+    _lib.call('nh_csr_spmm', ctypes.byref(_csr(values, rowptr, colidx, ncols, col32, lanes)), k, float(alpha), device.ptr(X), ldx, float(beta), device.ptr(B), ldb,
+              device.ptr(rowmask), device.ptr(Y), ldy, device.stream())
+    return Y
+
+
+def cgm_work(k):
+    '''the work array of a batched CG on k <= `MULTI_MAX` columns (nh_cgm_work_doubles): [0:k] = r . r of the recurrences, [k:2k] = breakdown flags, [2k:3k] = the
+    iterations since `cgm_init` that moved each column, [3k:4k] = the bounds of `cgm_stop`'''
+    size = _lib.load().nh_cgm_work_doubles(int(k))
+    if size < 0:
+        _lib.check(-1)
+    return device.empty(size, 'float64')
+
+
+def cgm_init(dinv, r, p, work):
+    '''per column of the contiguous (n, k) blocks: p = z = dinv r, first r . z and r . r; flags, counts and bounds cleared (nh_cgm_init)'''
+    n, k = r.shape
+    _lib.call('nh_cgm_init', n, k, device.ptr(dinv), device.ptr(r), device.ptr(p), device.ptr(work), device.stream())
+
+
+def cgm_stop(work, k, stop_rr):
+    '''after `cgm_init`: a column whose r . r <= stop_rr idles (work[3k:4k] of nh_cgm_iterate); `stop_rr` is one number for all columns or one each'''
+    work[3 * k:4 * k] = device.torch().as_tensor(stop_rr, dtype=work.dtype, device=work.device)
+
+
+def cgm_iterate(values, rowptr, colidx, ncols, *, rowmask, dinv, x, r, p, q, work, niter, col32=None, lanes=0):
+    '''enqueue `niter` iterations of the batched CG on the contiguous (n, k) blocks x, r, p, q (nh_cgm_iterate): three launches each for all columns, nothing
+    read back; a column stops moving once its r . r is within the bound of `cgm_stop`'''
+    n, k = x.shape
+    for name, t in (('x', x), ('r', r), ('p', p), ('q', q)):
+        if tuple(t.shape) != (n, k) or not t.is_contiguous():
+            raise ValueError(f'{name} must be a contiguous ({n}, {k}) block')
+    _lib.call('nh_cgm_iterate', ctypes.byref(_csr(values, rowptr, colidx, ncols, col32, lanes)), k, device.ptr(rowmask), device.ptr(dinv), device.ptr(x), device.ptr(r),
+              device.ptr(p), device.ptr(q), device.ptr(work), int(niter), device.stream())
+
+
 def bicgstab_work():
     '''the work array of a BiCGStab solve (nh_bicgstab_work_doubles): [0] = r . r of the recurrence, [1] = breakdown flag, [2] = iterations since
     `bicgstab_init` that moved x'''

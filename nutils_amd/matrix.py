@@ -16,7 +16,11 @@ run on the device (nh_csr.hip); ``function.eval(function.as_matrix(K))`` builds
 one without the triplet ever visiting the host, and so does ``solver.System``
 under this backend (``assemble_device``).  The matrix algebra runs there too
 (nh_csr_ops.hip): ``T``, ``submatrix`` by masks or strictly increasing indices,
-and sums of matrices with different patterns.  What a ``HipMatrix`` does
+and sums of matrices with different patterns.  Blocks of vectors have names of
+their own: ``matmat`` multiplies with an (ncols, k) block and
+``solve_columns`` solves for an (n, k) block of right-hand sides by batched
+conjugate gradients (nh_csr_multi.hip), reading the matrix once per eight
+columns.  What a ``HipMatrix`` does
 through scipy and a re-upload -- every solver other than 'cg', 'minres',
 'bicgstab' and 'fgmres', ``export``, ``submatrix`` by unordered or repeated
 integer indices -- says so in its docstring.
@@ -164,6 +168,11 @@ def _host(a):
     return device.to_host(a)
 
 
+def _row_major(t):
+    '''a 2-D device tensor as a block of vectors: itself if its columns are one double apart and its rows do not overlap, else a contiguous copy'''
+    return t if t.stride(1) == 1 and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1]) else t.contiguous()
+
+
 def _selector(sel, n, what):
     '''A selector of `submatrix` as a bool mask of length n: a bool array, or integers that rise strictly (numeric.asboolean of the reference, numeric.py:494).
     None for any other integer array in range (unordered, repeated, negative indices): those keep the host path.  Raises MatrixError for a wrong length, an
@@ -222,7 +231,10 @@ class HipMatrix:
     preconditioned by 1 / |diag|: one product a step, a residual that never rises in the norm it minimises, no breakdown short of the exhausted Krylov space;
     and for ANY square system (nonsymmetric, indefinite)
     `solve(solver='bicgstab')`, a Jacobi-preconditioned BiCGStab iteration, and `solve(solver='fgmres')`, Jacobi-preconditioned restarted GMRES, whose residual
-    norm never rises within a cycle; all with ONE right-hand side.  `iterations` is the iteration count of the last device solve.  Through scipy and PCIe (export, host operation, re-upload): every other solver, `submatrix` by
+    norm never rises within a cycle; all with ONE right-hand side per `solve`.  A block of vectors goes through names of its own, since `@` and `solve` refuse
+    2-D arguments: `matmat(X)` multiplies with an (ncols, k) block and `solve_columns(rhs)` solves for an (n, k) block of right-hand sides by k conjugate-gradient
+    recurrences (Jacobi or none) that share every pass over the matrix (nh_csr_spmm, nh_cgm_*: the values and column indices are read once per eight columns).
+    `iterations` is the iteration count of the last device solve, `column_iterations` the per-column counts of the last `solve_columns`.  Through scipy and PCIe (export, host operation, re-upload): every other solver, `submatrix` by
     integer indices that are not strictly increasing, and the algebra of a matrix made from host arrays in which a row repeats a column.'''
 
     def __init__(self, values, rowptr, colidx, ncols, *, validate=True):
@@ -243,6 +255,7 @@ class HipMatrix:
         self.lanes = spmv_lanes(nrows, nnz)
         self.cg_iterations = None
         self.iterations = None
+        self.column_iterations = None  # of the last `solve_columns`: the iterations that moved each column
         self._col32 = None
         self._canonical = True if self._hostcsr is None else None  # (`_unique`: None until a host triplet has been looked at)
         self._amg = None  # (free mask, coarse, k, levels) of the last 'amg' setup: the symbolic phase, reused while pattern and mask stay
@@ -310,6 +323,39 @@ class HipMatrix:
         from . import device
         y = self.spmv(other.contiguous() if on_device else device.to_dev(other, 'float64'))
         return y if on_device else device.to_host(y)
+
+    def spmm(self, X, *, alpha=1., beta=0., B=None, rowmask=None, Y=None, lanes=None):
+        '''Y = mask(alpha A X + beta B) on blocks of vectors, the device-level twin of `spmv` (nh_csr_spmm): 2-D float64 device tensors with unit column stride and
+        any row stride, so a column slice of a wider tensor will do; `B` may be `Y`.  Column j is, bit for bit, `spmv` of column j.'''
+        from . import kernels
+        values, rowptr, colidx = self.triplet()
+        return kernels.csr_spmm(values, rowptr, colidx, self._ncols, X, Y=Y, alpha=alpha, beta=beta, B=B, rowmask=rowmask, col32=self._columns(),
+                                lanes=self.lanes if lanes is None else lanes)
+
+    def _block_argument(self, X, nrows, what):
+        '''a block of columns as the caller gave it, checked before anything is uploaded: (on_device, X) with X a float host array or a float64 device tensor of
+        shape (nrows, k), k >= 1'''
+        on_device = _is_tensor(X)
+        if X is None:
+            raise MatrixError(f'{what} is missing: a block of shape ({nrows}, k) is needed, the number of columns has to come from somewhere')
+        if not on_device:
+            X = numpy.asarray(X, dtype=float)
+        if X.ndim != 2 or X.shape[1] < 1:
+            raise MatrixError(f'{what} has shape {tuple(X.shape)}, expected ({nrows}, k) with k >= 1: a block of columns (one vector goes to `solve` or `@`)')
+        if X.shape[0] != nrows:
+            raise MatrixError(f'{what} shape {tuple(X.shape)} does not match matrix shape {self.shape[0]}x{self.shape[1]}')
+        if on_device and 'float64' not in str(X.dtype):
+            raise MatrixError(f'{what} must be a float64 tensor, got {X.dtype}')
+        return on_device, X
+
+    def matmat(self, X):
+        '''A @ X for a block X of shape (ncols, k), k >= 1 (the reference's Matrix.__matmul__ with a 2-D array; `@` itself takes one vector): the matrix is read
+        once per eight columns instead of once per column.  A numpy array gives a numpy array, a device tensor a device tensor.  A wrong shape or rank is a
+        MatrixError before anything is uploaded.'''
+        from . import device
+        on_device, X = self._block_argument(X, self.shape[1], 'the right operand')
+        Y = self.spmm(_row_major(X) if on_device else device.to_dev(X, 'float64'))
+        return Y if on_device else device.to_host(Y)
 
     def _diagonal_dev(self):
         from . import kernels
@@ -553,6 +599,108 @@ class HipMatrix:
             import warnings
             warnings.warn(str(e))
             return e.best
+
+    def solve_columns(self, rhs, *, lhs0=None, constrain=None, solver='cg', atol=0., rtol=0., precon='diag', maxiter=None, check=16, preconargs=None):
+        '''Solve A X = rhs for a block of right-hand sides, rhs of shape (n, k) with k >= 1 (the reference's Matrix.solve with trailing axes, matrix/_base.py:100-224;
+        `solve` itself takes one vector): several load cases on one matrix, solved by k independent conjugate-gradient recurrences that share every pass over
+        the matrix (nh_cgm_*, nh_csr_spmm), so the matrix is read once per iteration and eight columns instead of once per iteration and column.
+
+        `rhs`: a host array or a device tensor; None is not accepted.  `lhs0`: (n,), broadcast over the columns as the reference does, or (n, k).  `constrain`:
+        (n,) in the two conventions of `constraints`, one mask for all columns; float constraints set every column to the constrained values.  On offer:
+        solver='cg' with precon 'diag' (Jacobi) or None, for a SYMMETRIC POSITIVE DEFINITE matrix; every other solver, 'amg' and `preconargs` are a MatrixError
+        (they solve one right-hand side at a time, through `solve`), and so are a missing tolerance and a matrix that is not square -- all before any device work.
+
+        The stopping rule is the reference's: ONE bound for all columns of the call, max(atol, rtol max_j |r0_j|) with r0 = mask(rhs - A lhs), and every column
+        must meet it.  Columns go in groups of at most eight; a group is one batched solve by the host loop of solver='cg': the true residuals by one block
+        product, `check` iterations between two looks (one copy of 3k doubles), and once every column is within the bound by its recurrence the true residuals
+        again, from which the columns that are above it restart while the others idle.  A column within the bound does no arithmetic, so column j of the result is,
+        bit for bit, what `solve(rhs[:, j], atol=bound)` returns.  A block wider than eight columns is solved group by group on contiguous copies of its groups.
+        `maxiter` (default: the free dofs) bounds the iterations of a group.  Raises MatrixError('cg: matrix is not positive definite') or ('cg: non-finite
+        residual') for any column, ToleranceNotReached(best) with `best` of shape (n, k) when a column is above the bound after `maxiter` iterations.
+
+        Sets `iterations` (the iterations enqueued for the group that took most; they are shared by the columns of a group) and `column_iterations` (a list: the
+        iterations that moved each column, counted on the device, exact whatever `check` is).  Returns (n, k): a numpy array, or a device tensor if `rhs` was one.'''
+        nrows, ncols = self.shape
+        on_device, rhs = self._block_argument(rhs, nrows, 'right-hand side')
+        k = rhs.shape[1]
+        if nrows != ncols:
+            raise MatrixError(f'constrained matrix is not square: {nrows}x{ncols}')
+        offer = "solve_columns offers solver='cg' with precon='diag' or None"
+        if solver != 'cg':
+            raise MatrixError(f'{offer}; solver {solver!r} takes one right-hand side at a time (solve)')
+        if precon not in ('diag', None):
+            raise MatrixError(f'{offer}; the preconditioner {precon!r} takes one right-hand side at a time (solve)')
+        if preconargs is not None:
+            raise MatrixError(f"{offer}; preconargs are the arguments of precon='amg', which takes one right-hand side at a time (solve)")
+        if not (atol > 0 or rtol > 0):
+            raise MatrixError("solver 'cg' needs a tolerance: pass atol or rtol (an iterative solve has no machine-precision mode)")
+        lhs0 = _host(lhs0)
+        if lhs0 is not None:
+            lhs0 = numpy.asarray(lhs0, dtype=float)
+            if lhs0.shape not in ((ncols,), (ncols, k)):
+                raise MatrixError(f'initial block has shape {lhs0.shape}, expected ({ncols},) or ({ncols}, {k})')
+        constrain = _host(constrain)
+        free, held = constraints(ncols, constrain)  # (one mask for all columns; `held`: zero with the values of float constraints written in)
+        lhs = numpy.zeros((ncols, k))
+        if lhs0 is not None:
+            lhs[:] = lhs0 if lhs0.ndim == 2 else lhs0[:, None]
+        if constrain is not None and numpy.asarray(constrain).dtype != bool:
+            lhs[~free] = held[~free, None]
+        return self._cg_columns(rhs, free, lhs, atol, rtol, precon, int(free.sum()) if maxiter is None else int(maxiter), max(1, int(check)), on_device)
+
+    def _cg_columns(self, rhs, free, lhs, atol, rtol, precon, maxiter, check, on_device):
+        from . import device, kernels
+        n, k = lhs.shape
+        values, rowptr, colidx = self.triplet()
+        mask, x, b, dinv = self._krylov_setup(rhs if on_device else device.to_dev(rhs, 'float64'), free, lhs, precon, True)
+        csr = dict(rowmask=mask, dinv=dinv, col32=self._columns(), lanes=self.lanes)
+        groups = []
+        for k0 in range(0, k, kernels.MULTI_MAX):  # a group: contiguous blocks of its own (the whole block if there is one group), the right-hand side a view
+            cols = slice(k0, min(k0 + kernels.MULTI_MAX, k))
+            xg = x if k <= kernels.MULTI_MAX else x[:, cols].contiguous()
+            r, p, q = (device.torch().empty_like(xg) for _ in range(3))
+            groups.append(dict(cols=cols, k=xg.shape[1], x=xg, b=b[:, cols], r=r, p=p, q=q, work=kernels.cgm_work(xg.shape[1])))
+
+        def start(g):
+            '''the true residuals mask(rhs - A x) of a group and fresh recurrences from them; returns r . r per column'''
+            self.spmm(g['x'], alpha=-1., beta=1., B=g['b'], rowmask=mask, Y=g['r'])
+            kernels.cgm_init(dinv, g['r'], g['p'], g['work'])
+            rr = g['work'][:g['k']].tolist()
+            if not numpy.isfinite(rr).all():
+                raise MatrixError('cg: non-finite residual')
+            return rr
+
+        self.iterations, self.column_iterations = 0, [0] * k
+        first = [start(g) for g in groups]
+        stop_rr = max(atol, rtol * max(max(rr) for rr in first) ** .5) ** 2  # one bound for all columns (the device compares r . r with this number, and so does the host)
+        reached = True
+        for g, rr in zip(groups, first):
+            kg, it = g['k'], 0
+            while any(v > stop_rr for v in rr) and it < maxiter:
+                kernels.cgm_stop(g['work'], kg, stop_rr)  # (a column within the bound idles: iterated past convergence its r . z would underflow, a false breakdown)
+                while it < maxiter:
+                    steps = min(check, maxiter - it)
+                    kernels.cgm_iterate(values, rowptr, colidx, self._ncols, x=g['x'], r=g['r'], p=g['p'], q=g['q'], work=g['work'], niter=steps, **csr)
+                    it += steps
+                    head = g['work'][:3 * kg].tolist()
+                    rr, flags, moved = head[:kg], head[kg:2 * kg], head[2 * kg:]
+                    if any(flags):
+                        raise MatrixError('cg: matrix is not positive definite')
+                    if not numpy.isfinite(rr).all():
+                        raise MatrixError('cg: non-finite residual')
+                    if all(v <= stop_rr for v in rr):
+                        break
+                for j, m in enumerate(moved):  # (a start clears the device's counts)
+                    self.column_iterations[g['cols'].start + j] += int(m)
+                self.iterations = max(self.iterations, it)
+                rr = start(g)
+            reached = reached and all(v <= stop_rr for v in rr)
+            if g['x'] is not x:
+                x[:, g['cols']] = g['x']
+        result = x if on_device else device.to_host(x)
+        if not reached:
+            raise ToleranceNotReached(result)
+        return result
 
     def _krylov_setup(self, rhs, free, lhs, precon, on_device):
         '''(mask, x, b, dinv) of a device solve: the row mask of the free dofs (None: all), the start vector, the right-hand side, the inverse diagonal'''

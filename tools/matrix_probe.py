@@ -32,10 +32,15 @@
     plans (the median of five after a warm-up, the device synchronised: these calls wait for the host), and with the plan (HIP events over windows, as the
     product) -- beside the host path of the same matrix in the same process (`_transpose_host`, `_submatrix_host`, `_add_host` on a matrix without a host
     copy, so the export is in it, as it was before; timed once, it takes seconds), with the bytes each device operation has to move and what fraction of
-    8 TB/s that is.
+    8 TB/s that is,
+  * for blocks of vectors (section 'columns', not in the default; nh_csr_multi.hip): at k = 1, 2, 4, 8 columns the time of the block product `spmm` against k calls of
+    `spmv` in the same process, their windows alternating, with the algorithmic bytes of each -- nnz (8 + 4) + nrows 8 + k (nrows + ncols) 8 for the block product,
+    which reads every (value, column) pair once, k (nnz (8 + 4) + nrows 16 + ncols 8) for the k products -- and the time of a batched CG iteration against k
+    single-vector iterations (each timed call restores the residuals, starts the recurrences and enqueues 20 iterations, so that no window runs into convergence;
+    the time is that call over 20).
 
 Usage: python tools/matrix_probe.py [--matrices poisson128,elasticity96,elasticity64,elasticity48,bilinear2048,bilinear1024,p2vector32,p2vector16] [--scale 1.0]
-[--sections spmv,cg,bicgstab,fgmres,minres,amg,smoother,algebra] [--eigratios 4,10,30] [--eigsteps 5,10,20] [--out FILE]
+[--sections spmv,cg,bicgstab,fgmres,minres,amg,smoother,algebra,columns] [--eigratios 4,10,30] [--eigsteps 5,10,20] [--out FILE]
 (--scale shrinks every mesh for a quick look; --sections leaves parts out).  Not run by any test.'''
 import argparse
 import json
@@ -171,6 +176,8 @@ def probe(name, args):
         info['smoother'] = probe_smoother(A, free, mask, rhs_dev, res0, info, args)
     if 'algebra' in args.sections:
         info['algebra'] = probe_algebra(A, free, args)
+    if 'columns' in args.sections:
+        info['columns'] = probe_columns(A, free, mask, args)
     return info
 
 
@@ -309,6 +316,58 @@ def probe_cg(A, free, mask, rhs_dev, res0, info, args):
     device.synchronize()
     info['solve'].update(wall_ms=(time.perf_counter() - t0) * 1e3, iterations=A.cg_iterations)
     info['solve']['true_relative_residual'] = float(A.spmv(sol, alpha=-1., beta=1., b=rhs_dev, rowmask=mask).norm() / res0.norm())
+
+
+def probe_columns(A, free, mask, args):
+    '''blocks of k = 1, 2, 4, 8 vectors: the block product against k single products, a batched CG iteration against k single ones'''
+    import torch
+    from nutils_amd import kernels
+    values, rowptr, colidx = A.triplet()
+    nrows, ncols = A.shape
+    nnz = A.nnz
+    col32 = A._columns()
+    entry = 8 + (4 if col32 is not None else 8)  # bytes of a (value, column) pair as the kernels read it
+    csr = dict(rowmask=mask, col32=col32, lanes=A.lanes)
+    dinv = (1. / A._diagonal_dev()).masked_fill(mask == 0, 0.)
+    rng = numpy.random.default_rng(3)
+    steps = 20
+    out = {}
+    for k in (1, 2, 4, 8):
+        X = torch.from_numpy(rng.normal(size=(ncols, k))).cuda()
+        Y = torch.empty((nrows, k), dtype=torch.float64, device='cuda')
+        xs, y = [X[:, j].contiguous() for j in range(k)], torch.empty(nrows, dtype=torch.float64, device='cuda')
+        block = lambda: A.spmm(X, Y=Y)
+        singles = lambda: [A.spmv(xj, y=y) for xj in xs]
+        tb, ts = windows([block, singles], args.window)
+        bytes_block, bytes_singles = nnz * entry + nrows * 8 + k * (nrows + ncols) * 8, k * (nnz * entry + nrows * 16 + ncols * 8)
+        spmm, spmv = stats(tb), stats(ts)
+        spmm.update(bytes=bytes_block, GBs=bytes_block / spmm['us'] / 1e3)
+        spmv.update(bytes=bytes_singles, GBs=bytes_singles / spmv['us'] / 1e3)
+        # CG: the same residuals as a block and as k vectors
+        R0 = torch.from_numpy(rng.normal(size=(nrows, k)) * free[:, None]).cuda()
+        xb, R, P, Q = torch.zeros_like(R0), torch.empty_like(R0), torch.empty_like(R0), torch.empty_like(R0)
+        work = kernels.cgm_work(k)
+
+        def batched():
+            R.copy_(R0)
+            kernels.cgm_init(dinv, R, P, work)
+            kernels.cgm_iterate(values, rowptr, colidx, ncols, dinv=dinv, x=xb, r=R, p=P, q=Q, work=work, niter=steps, **csr)
+
+        r0s = [R0[:, j].contiguous() for j in range(k)]
+        state = [(r0, torch.zeros_like(r0), torch.empty_like(r0), torch.empty_like(r0), torch.empty_like(r0), kernels.cg_work()) for r0 in r0s]
+
+        def one_by_one():
+            for r0, x, r, p, q, w in state:
+                r.copy_(r0)
+                kernels.cg_init(dinv, r, p, w)
+                kernels.cg_iterate(values, rowptr, colidx, ncols, dinv=dinv, x=x, r=r, p=p, q=q, work=w, niter=steps, **csr)
+
+        cb, cs = windows([batched, one_by_one], args.window)
+        cgm, cg = stats([t / steps for t in cb]), stats([t / steps for t in cs])
+        out[str(k)] = dict(spmm=spmm, k_spmv=spmv, spmv_over_spmm=spmv['us'] / spmm['us'], bytes_ratio=bytes_singles / bytes_block,
+                           cgm_iteration=cgm, k_cg_iterations=cg, cg_over_cgm=cg['us'] / cgm['us'])
+        del X, Y, xs, R0, xb, R, P, Q, state, r0s
+    return out
 
 
 def nodes_of(info):
