@@ -847,6 +847,11 @@ int nh_gmres_update(int64_t n, int restart, const double *dinv_dev, const double
  * geometry a function of sizes only, repeated calls bit-identical, argument errors NH_EINVAL before a launch, empty sizes no launch.
  * nh_segment_dot: out[s] = sum of a[ia[k]] * b[ib[k]] over k = ptr[s] .. ptr[s + 1] - 1, s < nseg; b_dev NULL: the plain segment sum of a[ia[k]].  ptr int64
  * [nseg + 1], ia / ib int32 [nprod], nprod = ptr[nseg].  Lanes per segment follow from the mean segment length by the rule of nh_csr_lanes.
+ * nh_block_segment_dot: the same sum over blocks that lie in scalar value arrays, 1 <= k <= 6, p and q each 1 or k: segment s < nseg is the block (p x k) with
+ * the entries out[of[s] + r os[s] + c], the sum over k' = ptr[s] .. ptr[s + 1] - 1, in that order and t ascending within, of a[ia[k'] + r sa[s] + t] *
+ * b[ib[k'] + t sb[k'] + c], r < p, t < q, c < k.  ptr int64 [nseg + 1]; ia, ib, sb int32 [nprod]; sa, of, os int32 [nseg].  sa and os may be NULL for p = 1;
+ * sb may be NULL for q = 1, and for q = k when every block of b has the row stride `bstride` >= k.  Every index must lie inside its array and the output
+ * blocks must not overlap: that is the caller's to see to.  One lane per entry of an output block.
  * nh_aggregate_qr: the thin QR of a near-nullspace B_dev [n x k] row-major, 1 <= k <= 6, on the rows of every aggregate: aggregate a < nagg has the rows
  * midx[mptr[a]] .. midx[mptr[a + 1] - 1] (mptr int64 [nagg + 1], midx int32 [nmembers], nmembers = mptr[nagg]; every row below n, in at most one aggregate).
  * Q_dev [n x k] row-major gets the orthonormal columns on the rows of each aggregate and 0 on rows in none; Rc_dev [nagg k x k] row-major gets block a =
@@ -902,6 +907,9 @@ typedef struct {
 
 int nh_segment_dot(int64_t nseg, const int64_t *ptr_dev, const int32_t *ia_dev, const int32_t *ib_dev, const double *a_dev, const double *b_dev, int64_t nprod,
                    double *out_dev, void *stream);
+int nh_block_segment_dot(int k, int p, int q, int64_t nseg, const int64_t *ptr_dev, int64_t nprod, const int32_t *ia_dev, const int32_t *ib_dev,
+                         const int32_t *sa_dev, const int32_t *sb_dev, int bstride, const int32_t *of_dev, const int32_t *os_dev, const double *a_dev,
+                         const double *b_dev, double *out_dev, void *stream);
 int nh_aggregate_qr(int64_t nagg, const int64_t *mptr_dev, const int32_t *midx_dev, int64_t nmembers, int k, int64_t n, const double *B_dev, double *Q_dev,
                     double *Rc_dev, void *stream);
 int nh_csr_jacobi(const nh_csr *A, const double *x_dev, const double *w_dev, const double *b_dev, const unsigned char *rowmask_dev, double *y_dev, void *stream);

@@ -232,6 +232,7 @@ SIGNATURES = {
     'nh_gmres_iterate': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, vp]),
     'nh_gmres_update': (ctypes.c_int, [c_i64, ctypes.c_int, vp, vp, vp, vp, vp]),
     'nh_segment_dot': (ctypes.c_int, [c_i64, vp, vp, vp, vp, vp, c_i64, vp, vp]),
+    'nh_block_segment_dot': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i64, vp, c_i64, vp, vp, vp, vp, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
     'nh_aggregate_qr': (ctypes.c_int, [c_i64, vp, vp, c_i64, ctypes.c_int, c_i64, vp, vp, vp, vp]),
     'nh_csr_jacobi': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, vp, vp, vp, vp]),
     'nh_csr_chebyshev': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, vp, vp, vp, vp, vp, vp, vp]),

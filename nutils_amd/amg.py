@@ -4,7 +4,7 @@ Two phases.  ``symbolic`` reads the pattern and the constraint mask only and is 
 live (on the device in a solve, on CPU tensors in the tests): the aggregates, the CSR patterns of the prolongator P, the restriction R = P^T and the
 coarse matrix A_c = R A P, and for each of the products A T, A P and R (A P) an expand-sort-compress plan -- the products of the sparse product listed,
 sorted stably by output entry and cut into segments.  ``numeric`` reads values, on the device: every sparse product is one nh_segment_dot over its
-plan, the step from A T to P and to the smoother's weights is elementwise, and the only matrix that visits the host is the coarsest (at most
+plan (one nh_block_segment_dot with the block plans at the end of this text), the step from A T to P and to the smoother's weights is elementwise, and the only matrix that visits the host is the coarsest (at most
 ``coarse``^2 doubles over PCIe), whose pseudo-inverse is computed there by numpy and applied on the device as a dense product.  With the Chebyshev
 smoother a level also sends the host the coefficients of its Lanczos recurrence (2 eigsteps + 1 doubles) and its rho, and gets 2 degree doubles back.
 
@@ -46,8 +46,17 @@ prolongator  T has k columns per aggregate: on the rows of aggregate a, the colu
              The triangles R, stacked, are the B of the coarse level, which has k dofs per aggregate and no mask.  P, R = P^T and A_c as above.
 dropped      the coarse dof of a dropped column has a zero column of P, a zero row and column of A_c: dinv = 0 there, the smoother leaves it alone and the
              pseudo-inverse of the dense level ignores it.
-termination  at most ``coarse`` free dofs: dense; as many aggregates as free nodes: z = dinv b, exact for k = 1 and symmetric positive semidefinite always.'''
+termination  at most ``coarse`` free dofs: dense; as many aggregates as free nodes: z = dinv b, exact for k = 1 and symmetric positive semidefinite always.
+block plans  ``preconargs=dict(nullspace=B, setup='block')``.  With k vectors the patterns are blocks by construction: the columns of every row of P and A P come in
+             full groups a k .. a k + k - 1, A_c and every level matrix below the finest are made of full k x k blocks.  'entry' (the default, the plans above) lists
+             every scalar product; 'block' runs the symbolic phase on the quotient (rows grouped by node, the columns of T, P and A P by aggregate) and lists one
+             product per pair of blocks (``BlockPlan``): k (A T, A P) and k^2 (R (A P)) times fewer on level 0, k^3 times fewer below.  From the block patterns it
+             derives the same integers 'entry' makes (the patterns of P, R, A P and A_c, tmap, rperm), and for every block its first entry and its row stride in
+             the scalar CSR value array, which is where nh_block_segment_dot reads and writes: the cycle reads scalar CSR either way.  That rests on the rows of a
+             node having one length and one set of columns, in full groups: ``node_blocks`` checks it on every level and raises MatrixError otherwise.  Without
+             `setup`, a near-nullspace and an entry plan whose product count reaches MAX_NPROD make the whole hierarchy again as 'block'.'''
 
+import functools
 import numpy
 
 MAX_COARSE = 1024  # the dense kernel's limit (nh_amg.hip)
@@ -122,9 +131,21 @@ def aggregate(rowptr, colidx, free=None):
     return agg, int(root.sum()), rounds
 
 
-def _check_nprod(nprod):
-    if nprod >= 1 << 31:
-        raise _error()(f'a sparse product of {nprod} terms exceeds the int32 indices of its plan')
+MAX_NPROD = 1 << 31  # what the int32 indices of a plan can count
+
+
+@functools.lru_cache(maxsize=None)
+def _overflow():
+    '''the MatrixError of a plan that outgrows its indices: what ``symbolic(..., setup=None)`` answers with block plans, and nothing else'''
+    return type('PlanOverflow', (_error(),), {})
+
+
+def _check_nprod(nprod, blocks=False):
+    if nprod >= MAX_NPROD:
+        if blocks:
+            raise _error()(f'a sparse product of {nprod} block terms, or an offset of {nprod} into its value arrays, exceeds the int32 indices of its plan')
+        raise _overflow()(f"a sparse product of {nprod} terms exceeds the int32 indices of its plan; with a near-nullspace, preconargs=dict(setup='block') states "
+                          'the plans over blocks, k to k^3 times fewer terms')
 
 
 class Plan:
@@ -146,11 +167,11 @@ class Plan:
         self.nseg, self.nprod = ukey.numel(), nprod
 
 
-def _expand(index, ptr):
+def _expand(index, ptr, blocks=False):
     '''for every i and every position m of ptr[index[i]] .. ptr[index[i] + 1] - 1: (i, m), i ascending and m ascending within i'''
     torch = _torch()
     count = ptr[index + 1] - ptr[index]
-    _check_nprod(int(count.sum()))  # (before the lists are made, not after: they are what runs out of memory)
+    _check_nprod(int(count.sum()), blocks)  # (before the lists are made, not after: they are what runs out of memory)
     src = torch.repeat_interleave(torch.arange(index.numel(), dtype=torch.int64, device=index.device), count)
     start = torch.cumsum(count, 0) - count
     return src, ptr[index][src] + torch.arange(src.numel(), dtype=torch.int64, device=index.device) - start[src]
@@ -162,7 +183,8 @@ class Level:
     rperm that takes the values of P to those of R, and R's pattern (rrowptr, rcol); the plans at (A T), ap (A P) and rap (R (A P)), whose output entries
     are the patterns of P, A P and A_c.  With a near-nullspace of k vectors (`k`; None without): nodesize (1 on level 0, k below: the dofs of a node), nagg,
     nc = nagg k, the free dofs aggregate by aggregate (mptr, midx), the plan `at` with two factors, a[e] T[acol[e], j] on T's value array [n x k], and
-    instead of tind the map tmap from the entries of P into that array (-1: none).'''
+    instead of tind the map tmap from the entries of P into that array (-1: none).  `setup`: 'entry' or 'block', the kind of plans the hierarchy was made
+    with; of a 'block' level at, ap and rap are `BlockPlan`s, every other integer is what 'entry' makes.'''
 
 
 def _node_graph(rowptr, colidx, size):
@@ -174,15 +196,34 @@ def _node_graph(rowptr, colidx, size):
     return _rowptr(rows, nnodes), key - rows * nnodes
 
 
+def _aggregate_nodes(lv):
+    '''agg, nagg, rounds and nc of a level; returns the aggregate of every node'''
+    torch = _torch()
+    if lv.k is None or lv.nodesize == 1:
+        lv.agg, lv.nagg, lv.rounds = aggregate(lv.rowptr, lv.colidx, lv.free)
+        nodeagg = lv.agg
+    else:  # a coarse level of a hierarchy with a near-nullspace: the k dofs of a node stay together
+        nodeagg, lv.nagg, lv.rounds = aggregate(*_node_graph(lv.rowptr, lv.colidx, lv.nodesize))
+        lv.agg = nodeagg[torch.div(torch.arange(lv.n, dtype=torch.int64, device=lv.rowptr.device), lv.nodesize, rounding_mode='floor')]
+    lv.nc = lv.nagg * (lv.k or 1)
+    return nodeagg
+
+
+def _members(lv):
+    '''mptr, midx: the free dofs aggregate by aggregate, ascending within one: what nh_aggregate_qr walks'''
+    torch = _torch()
+    dofs = torch.arange(lv.n, dtype=torch.int64, device=lv.rowptr.device) if lv.free is None else torch.nonzero(lv.free).reshape(-1)
+    sagg, order = torch.sort(lv.agg[dofs], stable=True)
+    lv.mptr, lv.midx = _rowptr(sagg, lv.nagg), dofs[order].to(torch.int32)
+
+
 def _coarsen(lv):
+    if lv.setup == 'block':
+        return _coarsen_blocks(lv)
     torch = _torch()
     rowptr, colidx, free, n, nk = lv.rowptr, lv.colidx, lv.free, lv.n, lv.k
-    if nk is None or lv.nodesize == 1:
-        lv.agg, lv.nagg, lv.rounds = aggregate(rowptr, colidx, free)
-    else:  # a coarse level of a hierarchy with a near-nullspace: the k dofs of a node stay together
-        nodeagg, lv.nagg, lv.rounds = aggregate(*_node_graph(rowptr, colidx, lv.nodesize))
-        lv.agg = nodeagg[torch.div(torch.arange(n, dtype=torch.int64, device=rowptr.device), lv.nodesize, rounding_mode='floor')]
-    nc = lv.nc = lv.nagg * (nk or 1)
+    _aggregate_nodes(lv)
+    nc = lv.nc
     rows = _rows(rowptr)
     k = torch.arange(colidx.numel(), dtype=torch.int64, device=colidx.device)
     if free is not None:
@@ -194,9 +235,7 @@ def _coarsen(lv):
         if n * nk >= 1 << 31:
             raise _error()(f'{n} dofs times {nk} near-nullspace vectors exceed the int32 indices of the plans')
         _check_nprod(k.numel() * nk)
-        dofs = torch.arange(n, dtype=torch.int64, device=rowptr.device) if free is None else torch.nonzero(free).reshape(-1)
-        sagg, order = torch.sort(lv.agg[dofs], stable=True)  # the free dofs aggregate by aggregate, ascending within one: what nh_aggregate_qr walks
-        lv.mptr, lv.midx = _rowptr(sagg, lv.nagg), dofs[order].to(torch.int32)
+        _members(lv)
         j = torch.arange(nk, dtype=torch.int64, device=rowptr.device).repeat(k.numel())
         ke, re, ce = (t.repeat_interleave(nk) for t in (k, arow, acol))
         lv.at = Plan(re, lv.agg[ce] * nk + j, nc, ke, ce * nk + j)  # (A T)[i, agg(c) k + j] = sum over the entries (i, c) of a[e] T[c, j], T = Q [n x k]
@@ -219,6 +258,146 @@ def _coarsen(lv):
     return _rowptr(lv.rap.rows, nc), lv.rap.cols
 
 
+# ---- the same three products stated over blocks (setup='block') ------------------------------------------------------------
+
+class BlockPlan:
+    '''expand-sort-compress plan of a sparse product over blocks that lie in scalar CSR value arrays (nh_block_segment_dot): segment s is the output block
+    (p x k) at out[of[s] + r os[s] + c], the sum over the products m = ptr[s] .. ptr[s + 1] - 1 of the block (p x q) at a[ia[m] + r sa[s] + t] times the block
+    (q x k) at b[ib[m] + t sb[m] + c]; sb None: the stride `bstride` for all of them.  p and q are 1 or k.  brows / bcols: the output block of each segment,
+    sorted by (row, column); of, os and sa are the caller's to fill in once the output's layout is known (`_layout`), nout being its scalar size.'''
+
+    def __init__(self, k, p, q, out_brows, out_bcols, nbcols, ia, ib, sb=None, bstride=0):
+        torch = _torch()
+        nprod = ia.numel()
+        _check_nprod(nprod, True)
+        key, order = torch.sort(out_brows * nbcols + out_bcols, stable=True)
+        ukey, counts = torch.unique_consecutive(key, return_counts=True)
+        self.ptr = torch.zeros(ukey.numel() + 1, dtype=torch.int64, device=ia.device)
+        torch.cumsum(counts, 0, out=self.ptr[1:])
+        self.ia, self.ib = ia[order].to(torch.int32), ib[order].to(torch.int32)
+        self.sb = None if sb is None else sb[order].to(torch.int32)
+        self.brows = torch.div(ukey, nbcols, rounding_mode='floor')
+        self.bcols = ukey - self.brows * nbcols
+        self.k, self.p, self.q, self.bstride = k, p, q, bstride
+        self.nseg, self.nprod, self.nout = ukey.numel(), nprod, ukey.numel() * p * k
+        self.sa = self.of = self.os = None
+
+    def scalar_pattern(self):
+        '''(rows, cols) of the output's scalar entries, in the order of its value array'''
+        return _scalar_pattern(self.brows, self.bcols, self.of, self.os, self.p, self.k)
+
+
+def _layout(brows, nbrows, p, s):
+    '''where the blocks (p x s) of a block pattern sorted by (row, column) lie in the scalar CSR of the same matrix: (first, stride, bptr, rowptr) -- the
+    first entry of every block, the row stride of every block ROW (the length of its scalar rows), the block row pointers and the scalar ones'''
+    torch = _torch()
+    bptr = _rowptr(brows, nbrows)
+    cnt = bptr[1:] - bptr[:-1]
+    _check_nprod(brows.numel() * p * s, True)
+    first = (bptr[brows] * (p - 1) + torch.arange(brows.numel(), dtype=torch.int64, device=brows.device)) * s  # ((bptr[I] p + position in the row) s)
+    stride = cnt * s
+    rowptr = torch.empty(nbrows * p + 1, dtype=torch.int64, device=brows.device)
+    rowptr[:-1] = ((bptr[:-1] * (p * s)).reshape(-1, 1) + torch.arange(p, dtype=torch.int64, device=brows.device) * stride.reshape(-1, 1)).reshape(-1)
+    rowptr[-1] = brows.numel() * p * s
+    return first, stride, bptr, rowptr
+
+
+def _block_entries(first, stride, p, s):
+    '''the index of entry (r, c) of every block in the scalar value array: [blocks, p, s]'''
+    torch = _torch()
+    r, c = (torch.arange(m, dtype=torch.int64, device=first.device) for m in (p, s))
+    return first.reshape(-1, 1, 1) + r.reshape(1, -1, 1) * stride.reshape(-1, 1, 1) + c.reshape(1, 1, -1)
+
+
+def _scalar_pattern(brows, bcols, first, stride, p, s):
+    '''(rows, cols): the scalar entries of the blocks (p x s), in the order of the value array; stride: of every block'''
+    torch = _torch()
+    idx = _block_entries(first.to(torch.int64), stride.to(torch.int64), p, s)
+    rows, cols = torch.empty(idx.numel(), dtype=torch.int64, device=idx.device), torch.empty(idx.numel(), dtype=torch.int64, device=idx.device)
+    r, c = (torch.arange(m, dtype=torch.int64, device=idx.device) for m in (p, s))
+    rows[idx.reshape(-1)] = (brows.reshape(-1, 1, 1) * p + r.reshape(1, -1, 1)).expand(idx.shape).reshape(-1)
+    cols[idx.reshape(-1)] = (bcols.reshape(-1, 1, 1) * s + c.reshape(1, 1, -1)).expand(idx.shape).reshape(-1)
+    return rows, cols
+
+
+def node_blocks(rowptr, colidx, size):
+    '''(brows, bcols, first, length): the blocks (size x size) of a level matrix whose node I is the dofs I size .. I size + size - 1, sorted by (row, column),
+    the position `first` of the first entry of each in the scalar value array, and the length of every scalar row (the row stride of the blocks of its node).
+    This CHECKS what the block kernel relies on, since it writes where these integers point: the rows of a node have one length and one set of columns, and
+    the columns come in full groups J size .. J size + size - 1.  MatrixError otherwise.'''
+    torch = _torch()
+    n = rowptr.numel() - 1
+    length = rowptr[1:] - rowptr[:-1]
+    rows = _rows(rowptr)
+    e = torch.arange(colidx.numel(), dtype=torch.int64, device=colidx.device)
+    t = e - rowptr[rows]  # the position in the row
+    head = rows - rows % size  # the first dof of the node
+    ok = n % size == 0 and bool((length == length[torch.arange(n, dtype=torch.int64, device=rowptr.device) // size * size]).all()) and bool((length % size == 0).all())
+    if ok:
+        j = t % size
+        ok = bool((colidx == colidx[rowptr[head] + t]).all()) and bool((colidx % size == j).all()) and bool((colidx - j == colidx[e - j]).all())
+    if not ok:
+        raise _error()(f"amg: setup='block' needs a level matrix made of full {size} x {size} blocks, rows of a node with one length and one set of columns; "
+                       "this one is not (setup='entry' makes no such assumption)")
+    lead = (rows % size == 0) & (t % size == 0)
+    first = e[lead]
+    return rows[first] // size, colidx[first] // size, first, length
+
+
+def _coarsen_blocks(lv):
+    '''`_coarsen` on the quotient: rows grouped by node, the columns of T, P and A P by aggregate, one product per pair of blocks; from the block patterns the
+    integers of the scalar CSRs that `_coarsen` makes, the same'''
+    torch = _torch()
+    rowptr, colidx, free, n, nk, ns = lv.rowptr, lv.colidx, lv.free, lv.n, lv.k, lv.nodesize
+    i64 = dict(dtype=torch.int64, device=rowptr.device)
+    nodeagg = _aggregate_nodes(lv)
+    nagg, nn = lv.nagg, n // ns
+    if n * nk >= MAX_NPROD:
+        raise _error()(f'{n} dofs times {nk} near-nullspace vectors exceed the int32 indices of the plans')
+    _check_nprod(colidx.numel(), True)
+    _members(lv)
+    if ns == 1:  # the entries of A_f, blocks of one entry
+        rows = _rows(rowptr)
+        first = torch.arange(colidx.numel(), **i64)
+        if free is not None:
+            first = first[free[rows] & free[colidx]]
+        brows, bcols, length = rows[first], colidx[first], None
+    else:
+        if free is not None:
+            raise _error()('amg: a level with nodes of several dofs has no mask')
+        brows, bcols, first, length = node_blocks(rowptr, colidx, ns)
+        length = length[::ns]  # of every node
+    sa = lambda plan: None if ns == 1 else length[plan.brows].to(torch.int32)
+    # A T: the block (I, J) of A times the rows of node J of Q [n x k]
+    at = lv.at = BlockPlan(nk, ns, ns, brows, nodeagg[bcols], nagg, first, bcols * (ns * nk), None, nk)
+    pfirst, pstride, pbptr, lv.prowptr = _layout(at.brows, nn, ns, nk)
+    pbrows, pbcols = at.brows, at.bcols
+    at.sa, at.of, at.os = sa(at), pfirst.to(torch.int32), pstride[pbrows].to(torch.int32)
+    lv.prow, lv.pcol = at.scalar_pattern()
+    block = torch.div(lv.pcol, nk, rounding_mode='floor')
+    lv.tmap = torch.where(block == lv.agg[lv.prow], lv.prow * nk + (lv.pcol - block * nk), -1)
+    # A P: the block (I, J) of A times every block of the block row J of P
+    src, m = _expand(bcols, pbptr, True)
+    ap = lv.ap = BlockPlan(nk, ns, ns, brows[src], pbcols[m], nagg, first[src], pfirst[m], None if ns == 1 else pstride[pbrows[m]])
+    apfirst, apstride, apbptr, _ = _layout(ap.brows, nn, ns, nk)
+    ap.sa, ap.of, ap.os = sa(ap), apfirst.to(torch.int32), apstride[ap.brows].to(torch.int32)
+    # R = P^T: its blocks (k x nodesize) sorted by (aggregate, node), each entry from its twin in P
+    _, bperm = torch.sort(pbcols * nn + pbrows, stable=True)
+    rbrows, rbcols = pbcols[bperm], pbrows[bperm]
+    rfirst, rstride, _, lv.rrowptr = _layout(rbrows, nagg, nk, ns)
+    twin = _block_entries(pfirst[bperm], pstride[rbcols], ns, nk).transpose(1, 2)  # [blocks, k, nodesize]: the entry (r, j) of P's block at (j, r)
+    lv.rperm = torch.empty(twin.numel(), **i64)
+    lv.rperm[_block_entries(rfirst, rstride[rbrows], nk, ns).reshape(-1)] = twin.reshape(-1)
+    rrow, lv.rcol = _scalar_pattern(rbrows, rbcols, rfirst, rstride[rbrows], nk, ns)
+    lv.pcol32, lv.rcol32 = lv.pcol.to(torch.int32), lv.rcol.to(torch.int32)
+    # R (A P): the block (a, I) of R times every block of the block row I of A P
+    src, m = _expand(rbcols, apbptr, True)
+    rap = lv.rap = BlockPlan(nk, nk, ns, rbrows[src], ap.bcols[m], nagg, rfirst[src], apfirst[m], None if ns == 1 else apstride[ap.brows[m]])
+    acfirst, acstride, _, acrowptr = _layout(rap.brows, nagg, nk, nk)
+    rap.sa, rap.of, rap.os = (None if nk == 1 else rstride[rap.brows].to(torch.int32)), acfirst.to(torch.int32), acstride[rap.brows].to(torch.int32)
+    return acrowptr, rap.scalar_pattern()[1]
+
+
 def _dense_block(lv):
     '''the free block of a dense level, selected where the pattern lies: dk the positions of its entries in the value array, (drow, dcol) their place in the
     nfree x nfree matrix (free dofs renumbered in ascending order), idx32 the free dofs (None: all).  At most nfree^2 entries: what of this level goes to the host.'''
@@ -233,14 +412,46 @@ def _dense_block(lv):
         lv.idx32 = torch.nonzero(lv.free).reshape(-1).to(torch.int32)
 
 
-def symbolic(rowptr, colidx, free=None, coarse=256, nullspace=None):
+SETUPS = None, 'entry', 'block'
+
+
+def check_setup(setup, nullspace):
+    '''`setup` validated against the near-nullspace (anything that is None without one)'''
+    if not (setup is None or isinstance(setup, str)) or setup not in SETUPS:
+        raise _error()(f"amg: setup must be 'entry', 'block' or None, got {setup!r}")
+    if setup == 'block' and nullspace is None:
+        raise _error()("amg: setup='block' states the plans over the k x k blocks of a near-nullspace and needs `nullspace`; with the constant the entry plans "
+                       'are the block plans')
+    return setup
+
+
+def split_setup(preconargs):
+    '''(rest, setup): the key 'setup' of `preconargs` taken out and validated, the others left for `check_args`'''
+    rest = dict(preconargs or {})
+    setup = rest.pop('setup', None)
+    return rest, check_setup(setup, rest.get('nullspace'))
+
+
+def symbolic(rowptr, colidx, free=None, coarse=256, nullspace=None, *, setup=None):
     '''The levels of the hierarchy of a pattern and a mask (`free`: bool tensor, True on free dofs; None: all): a list of `Level`, the last of which is
     'dense' or 'diagonal'.  `nullspace`: the number k of near-nullspace vectors the numeric phase will be given (None: the constant, on every level).  No
-    value is read.'''
+    value is read.  `setup`: 'entry' (plans over scalar products), 'block' (over block products; needs `nullspace`) or None: 'entry', unless there is a
+    near-nullspace and a product count of the entry plans reaches MAX_NPROD -- then the whole hierarchy is made again as 'block'.'''
+    check_setup(setup, nullspace)
+    if setup is None and nullspace is not None:
+        try:
+            return _symbolic(rowptr, colidx, free, coarse, nullspace, 'entry')
+        except _overflow():  # (the count of a plan, known before its lists exist; no other MatrixError)
+            return _symbolic(rowptr, colidx, free, coarse, nullspace, 'block')
+    return _symbolic(rowptr, colidx, free, coarse, nullspace, setup or 'entry')
+
+
+def _symbolic(rowptr, colidx, free, coarse, nullspace, setup):
     torch = _torch()
     levels = []
     while True:
         lv = Level()
+        lv.setup = setup
         lv.rowptr, lv.colidx, lv.free = rowptr, colidx, free
         lv.n = rowptr.numel() - 1
         lv.nfree = lv.n if free is None else int(free.sum())
@@ -423,16 +634,17 @@ class Hierarchy:
             d.rho = (absrow * d.dinv).max()
             d.omega = 4. / (3. * d.rho)
             d.w = d.omega * d.dinv
+            product = kernels.block_segment_dot if lv.setup == 'block' else kernels.segment_dot  # (the plans of a level are of one kind)
             if nk is None:
                 d.atvalues = kernels.segment_dot(lv.at, values)
                 d.pvalues = lv.tind - d.w[lv.prow] * d.atvalues
             else:
                 d.q, B = kernels.aggregate_qr(lv.mptr, lv.midx, nk, B)
                 flat = d.q.reshape(-1)
-                d.atvalues = kernels.segment_dot(lv.at, values, flat)
+                d.atvalues = product(lv.at, values, flat)
                 d.pvalues = flat[lv.tmap.clamp(min=0)].masked_fill(lv.tmap < 0, 0.) - d.w[lv.prow] * d.atvalues
             d.rvalues = d.pvalues[lv.rperm]
-            d.apvalues = kernels.segment_dot(lv.ap, values, d.pvalues)
+            d.apvalues = product(lv.ap, values, d.pvalues)
             d.t, d.r = device.empty(lv.n, 'float64'), device.empty(lv.n, 'float64')
             if smoother is not None:
                 # PCIe: the alpha and beta of the recurrence and its step count visit the host, and so does rho, one number
@@ -447,7 +659,7 @@ class Hierarchy:
                 d.d = device.empty(lv.n, 'float64')
                 desc.update(smoother='chebyshev', degree=smoother['degree'], coef=d.coef, d=d.d)
             desc.update(kind='coarsen', w=d.w if smoother is None else d.dinv, t=d.t, r=d.r, P=(d.pvalues, lv.prowptr, lv.pcol, lv.nc, lv.pcol32, 0), R=(d.rvalues, lv.rrowptr, lv.rcol, lv.n, lv.rcol32, 0))
-            values = kernels.segment_dot(lv.rap, d.rvalues, d.apvalues)
+            values = product(lv.rap, d.rvalues, d.apvalues)
         self.handle = kernels.Amg(descriptions)
 
     def apply(self, r, z=None):

@@ -7,6 +7,9 @@
 //     products have been listed and sorted by output entry beforehand.  L lanes own a segment, consecutive lane groups take consecutive segments (so a
 //     wave reads one contiguous span of the index arrays), segments longer than L are walked in strides of L and folded with __shfl_xor: the mapping
 //     of k_csr_spmv.  It evaluates A T, A P and R (A P) of every level.
+//   * k_block_segment_dot<K, PK, QK>: the same products stated over blocks, for a hierarchy with a near-nullspace of K vectors: a segment is an output block
+//     (P x K), the sum of products of a block (P x Q) with a block (Q x K), P and Q each 1 or K; the blocks lie in scalar CSR value arrays and are found by
+//     their first entry and their row stride.  One lane per entry of an output block walks the segment; the index arrays are read once per block product.
 //   * k_aggregate_qr<L>: the aggregate-wise thin QR of a near-nullspace B [n x k], k <= 6, by Gram-Schmidt in two passes: Q [n x k] holds the values of the
 //     tentative prolongator, the triangles R are the near-nullspace of the next level.  L lanes own an aggregate (chosen from the mean size as above), rows
 //     strided over them, norms and dots folded with __shfl_xor.  Once per hierarchy build.
@@ -67,6 +70,37 @@ __global__ __launch_bounds__(WG) void k_segment_dot(i64 nseg, const i64 *__restr
 }
 
 constexpr int QR_MAXK = 6;
+
+// The sparse products of a hierarchy with a near-nullspace of K vectors, stated over blocks: segment s is the output block (P x K) at out[of[s] + r os[s] + c],
+// the sum over its products k of the block (P x Q) at a[ia[k] + r sa[s] + t] times the block (Q x K) at b[ib[k] + t sb[k] + c] (sb NULL: the stride bstride
+// for every product, the rows of Q [n x K]).  P and Q are 1 or K.  One lane owns one entry (r, c) of one output block and walks the products of its segment
+// in the order of the plan, t ascending within a product: one accumulator, nothing crosses lanes.  The P K lanes of a segment are neighbours, so they read the
+// same index words (one request) and the K consecutive doubles of a row of the second factor; the index arrays are read once per block product, where
+// k_segment_dot reads a pair for every multiply-add.
+template <int K, bool PK, bool QK>
+__global__ __launch_bounds__(WG) void k_block_segment_dot(i64 nseg, const i64 *__restrict__ ptr, const int32_t *__restrict__ ia, const int32_t *__restrict__ ib,
+                                                          const int32_t *__restrict__ sa, const int32_t *__restrict__ sb, int bstride,
+                                                          const int32_t *__restrict__ of, const int32_t *__restrict__ os, const double *__restrict__ a,
+                                                          const double *__restrict__ b, double *__restrict__ out) {
+  constexpr int P = PK ? K : 1, Q = QK ? K : 1, E = P * K;
+  const i64 total = nseg * E;
+  for (i64 g = (i64)blockIdx.x * WG + threadIdx.x; g < total; g += (i64)gridDim.x * WG) {
+    const i64 seg = g / E;
+    const int e = (int)(g - seg * E), r = e / K, c = e - r * K;
+    const i64 k1 = ptr[seg + 1];
+    const i64 arow = P > 1 ? (i64)r * sa[seg] : 0;
+    double s = 0;
+#pragma unroll 2
+    for (i64 k = ptr[seg]; k < k1; ++k) {
+      const double *ap = a + (ia[k] + arow);
+      const double *bp = b + ((i64)ib[k] + c);
+      const i64 st = Q > 1 ? (sb ? sb[k] : bstride) : 0;
+#pragma unroll
+      for (int t = 0; t < Q; ++t) s += ap[t] * bp[t * st];
+    }
+    out[of[seg] + (P > 1 ? (i64)r * os[seg] : 0) + c] = s;
+  }
+}
 
 template <int L>
 __device__ __forceinline__ double group_sum(double s) {
@@ -616,6 +650,52 @@ int nh_segment_dot(int64_t nseg, const int64_t *ptr_dev, const int32_t *ia_dev, 
     NH_SEGDOT(32)
   }
 #undef NH_SEGDOT
+  NH_LAUNCH_CHECK();
+  return NH_OK;
+}
+
+int nh_block_segment_dot(int k, int p, int q, int64_t nseg, const int64_t *ptr_dev, int64_t nprod, const int32_t *ia_dev, const int32_t *ib_dev,
+                         const int32_t *sa_dev, const int32_t *sb_dev, int bstride, const int32_t *of_dev, const int32_t *os_dev, const double *a_dev,
+                         const double *b_dev, double *out_dev, void *stream) {
+  NH_REQUIRE(k >= 1 && k <= QR_MAXK, "nh_block_segment_dot: k must be between 1 and %d (got %d)", QR_MAXK, k);
+  NH_REQUIRE((p == 1 || p == k) && (q == 1 || q == k), "nh_block_segment_dot: the blocks are p x q and q x k with p and q either 1 or k = %d (got p = %d, q = %d)", k, p, q);
+  NH_REQUIRE(nseg >= 0 && nprod >= 0, "nh_block_segment_dot: negative size");
+  NH_REQUIRE(!nseg || (ptr_dev && of_dev && out_dev), "nh_block_segment_dot: NULL segment pointers, result offsets or result");
+  NH_REQUIRE(!nseg || p == 1 || (sa_dev && os_dev), "nh_block_segment_dot: blocks of %d rows without the row strides of the first factor and of the result", p);
+  NH_REQUIRE(!nprod || (ia_dev && a_dev), "nh_block_segment_dot: NULL first factor");
+  NH_REQUIRE(!nprod || (ib_dev && b_dev), "nh_block_segment_dot: NULL second factor");
+  NH_REQUIRE(!nprod || q == 1 || sb_dev || bstride >= k, "nh_block_segment_dot: without its row strides the second factor needs a common one of at least k = %d (got %d)", k, bstride);
+  if (!nseg) return NH_OK;
+  hipStream_t s = nh_stream(stream);
+  const i64 *ptr = (const i64 *)ptr_dev;
+  const i64 total = (i64)nseg * p * k;
+  const unsigned grid = (unsigned)std::min<i64>((total + WG - 1) / WG, SPMV_MAX_WGS);
+  const bool pk = p > 1, qk = q > 1;
+#define NH_BLOCKDOT_AT(KK, PK, QK)                                                                                                                      \
+  hipLaunchKernelGGL((k_block_segment_dot<KK, PK, QK>), dim3(grid), dim3(WG), 0, s, (i64)nseg, ptr, ia_dev, ib_dev, sa_dev, sb_dev, bstride, of_dev, os_dev, \
+                     a_dev, b_dev, out_dev)
+#define NH_BLOCKDOT(KK)                    \
+  case KK:                                 \
+    if (pk && qk)                          \
+      NH_BLOCKDOT_AT(KK, true, true);      \
+    else if (pk)                           \
+      NH_BLOCKDOT_AT(KK, true, false);     \
+    else if (qk)                           \
+      NH_BLOCKDOT_AT(KK, false, true);     \
+    else                                   \
+      NH_BLOCKDOT_AT(KK, false, false);    \
+    break;
+  switch (k) {
+    NH_BLOCKDOT(1)
+    NH_BLOCKDOT(2)
+    NH_BLOCKDOT(3)
+    NH_BLOCKDOT(4)
+    NH_BLOCKDOT(5)
+    default:
+    NH_BLOCKDOT(6)
+  }
+#undef NH_BLOCKDOT
+#undef NH_BLOCKDOT_AT
   NH_LAUNCH_CHECK();
   return NH_OK;
 }

@@ -1085,6 +1085,48 @@ def segment_dot(plan, a, b=None, out=None):
     return out
 
 
+def block_segment_dot(plan, a, b, out=None):
+    '''the sparse product of a plan over blocks (`amg.BlockPlan`; nh_block_segment_dot): the output block (p x k) of segment s, at out[of[s] + r os[s] + c], is
+    the sum over its products m of the block (p x q) at a[ia[m] + r sa[s] + t] times the block (q x k) at b[ib[m] + t sb[m] + c] (sb None: the stride
+    plan.bstride).  `out`: plan.nout doubles when not given, zero where no block lies.  The indices are checked against the lengths of a, b and out here (one
+    look at the device, the first time a plan meets arrays of these lengths): the kernel reads and writes where they point.'''
+    import torch
+    k, p, q, nseg, nprod = int(plan.k), int(plan.p), int(plan.q), int(plan.nseg), int(plan.nprod)
+    if out is None:
+        out = device.zeros(int(plan.nout), 'float64')
+    for name, t in (('a', a), ('b', b), ('out', out)):
+        if t.dim() != 1 or not t.is_contiguous() or str(t.dtype) != 'torch.float64':
+            raise ValueError(f'block_segment_dot: {name} must be a contiguous float64 vector, got {tuple(t.shape)} {t.dtype}')
+    i32 = lambda t, size: t is not None and str(t.dtype) == 'torch.int32' and t.numel() == size
+    if str(plan.ptr.dtype) != 'torch.int64' or plan.ptr.numel() != nseg + 1 or not (i32(plan.ia, nprod) and i32(plan.ib, nprod) and i32(plan.of, nseg)):
+        raise ValueError('block_segment_dot: ptr must be int64 [nseg + 1], ia and ib int32 [nprod], of int32 [nseg]')
+    if p > 1 and not (i32(plan.sa, nseg) and i32(plan.os, nseg)):
+        raise ValueError('block_segment_dot: blocks of several rows need sa and os, int32 [nseg]')
+    if plan.sb is not None and not i32(plan.sb, nprod):
+        raise ValueError('block_segment_dot: sb must be int32 [nprod]')
+    lengths = a.numel(), b.numel(), out.numel()
+    if 1 <= k <= 6 and p in (1, k) and q in (1, k) and nseg and nprod and getattr(plan, 'checked', None) != lengths:  # (the rest is the C entry's to refuse)
+        i64 = lambda t: t.to(torch.int64)
+        alast = i64(plan.ia) + (q - 1)
+        if p > 1:  # the segment of every product, for the row stride of its first factor (clamped: a wrong ptr is found below, not followed)
+            seg = torch.searchsorted(plan.ptr[1:].clamp(0, nprod).to(torch.int32), torch.arange(nprod, dtype=torch.int32, device=a.device), right=True, out_int32=True)
+            alast += i64(plan.sa)[seg.clamp(max=nseg - 1).to(torch.int64)] * (p - 1)
+        blast = i64(plan.ib) + (i64(plan.sb) if plan.sb is not None else int(plan.bstride)) * (q - 1) + (k - 1)
+        olast = i64(plan.of) + (i64(plan.os) * (p - 1) if p > 1 else 0) + (k - 1)
+        lowest = [plan.ia, plan.ib, plan.of, plan.ptr[1:] - plan.ptr[:-1]] + ([plan.sa, plan.os] if p > 1 else []) + ([plan.sb] if plan.sb is not None else [])
+        first, last, lowest, *reach = torch.stack([plan.ptr[0], plan.ptr[-1], torch.stack([i64(t.min()) for t in lowest]).min(), alast.max(), blast.max(), olast.max()]).tolist()
+        if first != 0 or last != nprod or lowest < 0:
+            raise ValueError('block_segment_dot: ptr must rise from 0 to the number of products, and no index or stride may be negative')
+        for name, entry, length in zip(('a', 'b', 'out'), reach, lengths):
+            if entry >= length:
+                raise ValueError(f'block_segment_dot: a block reaches entry {entry} of {name}, which has {length}')
+        plan.checked = lengths  # (a plan is not written after it is made: the next numeric setup of these sizes does not look again)
+    _lib.call('nh_block_segment_dot', k, p, q, nseg, device.ptr(plan.ptr), nprod, device.ptr(plan.ia), device.ptr(plan.ib), device.ptr(plan.sa if p > 1 else None),
+              device.ptr(plan.sb), int(plan.bstride), device.ptr(plan.of), device.ptr(plan.os if p > 1 else None), device.ptr(a), device.ptr(b), device.ptr(out),
+              device.stream())
+    return out
+
+
 def aggregate_qr(mptr, midx, k, B):
     '''(Q, Rc): the thin QR of the near-nullspace `B` [n x k] on the rows of every aggregate (nh_aggregate_qr).  Aggregate a has the rows
     midx[mptr[a] : mptr[a + 1]] (int64 pointers, int32 rows, every row in at most one aggregate); Q [n x k] is 0 on rows in none, Rc [nagg k x k] holds the

@@ -258,7 +258,7 @@ class HipMatrix:
         self.column_iterations = None  # of the last `solve_columns`: the iterations that moved each column
         self._col32 = None
         self._canonical = True if self._hostcsr is None else None  # (`_unique`: None until a host triplet has been looked at)
-        self._amg = None  # (free mask, coarse, k, levels) of the last 'amg' setup: the symbolic phase, reused while pattern and mask stay
+        self._amg = None  # (free mask, coarse, k, levels, setup) of the last 'amg' setup: the symbolic phase, reused while pattern and mask stay
         self._tplan = None  # the index side of `T` (_Plan), made at the first transpose
         self._subplan = None  # the index side of the last `submatrix` (_Plan; its key: the two masks)
 
@@ -516,8 +516,11 @@ class HipMatrix:
         and after each coarse correction.  The near-nullspace is the constant unless `preconargs` has `nullspace=B`: a float64 host array or device tensor of
         shape (n, k), or (n,) for k = 1, with 1 <= k <= 6 finite vectors that the smoother reduces slowly -- for elasticity the rigid-body modes
         (`amg.rigid_body_modes(coords)`), without which a vector problem gets a valid preconditioner, not an optimal one.  Rows of constrained dofs are ignored;
-        a host array crosses PCIe once per solve, as n k doubles.  The symbolic phase runs once per pattern, mask, `coarse` and k and is handed on by
-        `_with_values`.  `preconargs` may name the smoother: `smoother='jacobi'` (the default: the `sweeps` above) or `smoother='chebyshev'` with
+        a host array crosses PCIe once per solve, as n k doubles.  The symbolic phase runs once per pattern, mask, `coarse`, k and `setup` and is handed on by
+        `_with_values`.  With a near-nullspace `preconargs` may name how the sparse products of the setup are planned: `setup='entry'` (one int32 pair per scalar
+        product; a plan of 2^31 products or more is a MatrixError) or `setup='block'` (one per product of k x k blocks, k to k^3 times fewer: what the large vector
+        problems need); without `setup` it is 'entry' unless a plan outgrows its indices, and then 'block' for the whole hierarchy.
+        `preconargs` may name the smoother: `smoother='jacobi'` (the default: the `sweeps` above) or `smoother='chebyshev'` with
         `degree=2` (1 .. 8: the steps of the polynomial before and after each coarse correction, a cycle costing what `sweeps=degree` costs), `eigsteps=10`
         (1 .. 64: the Lanczos steps that estimate the largest eigenvalue of D^-1 A on every level, run on the device at each numeric setup) and
         `eigratio=10.` (> 1: the polynomial damps the eigenvalues between the upper bound and its `eigratio`-th part).  `sweeps` other than 1 with 'chebyshev',
@@ -573,8 +576,9 @@ class HipMatrix:
             raise MatrixError(f"solver {solver!r} needs a tolerance: pass atol or rtol (an iterative solve has no machine-precision mode)")
         if precon == 'amg' and solver == 'cg':
             from . import amg
+            preconargs, setup = amg.split_setup(preconargs)
             preconargs, smoother = amg.split_smoother(preconargs)
-            preconargs = amg.check_args(preconargs, ncols) + (smoother,)
+            preconargs = amg.check_args(preconargs, ncols) + (smoother, setup)
         elif precon not in ('diag', None):
             raise MatrixError(f"invalid preconditioner {precon!r} for HipMatrix solver {solver!r}: 'diag' or None" + (", or 'amg'" if solver == 'cg' else ''))
         elif preconargs is not None:
@@ -718,14 +722,15 @@ class HipMatrix:
             dinv = (1. / diag).masked_fill(~keep | (diag == 0), 0.)  # (constrained rows: any finite number, their residual is zero)
         return mask, x, b, dinv
 
-    def _amg_hierarchy(self, free, mask, coarse, sweeps, nullspace=None, smoother=None):
-        '''the hierarchy of an 'amg' preconditioner (amg.Hierarchy): the symbolic phase is taken from the cache if it was made for this mask, this `coarse` and
-        this number of near-nullspace vectors, the numeric phase runs on the values of this matrix (the smoother belongs to it: the cache does not know it)'''
+    def _amg_hierarchy(self, free, mask, coarse, sweeps, nullspace=None, smoother=None, setup=None):
+        '''the hierarchy of an 'amg' preconditioner (amg.Hierarchy): the symbolic phase is taken from the cache if it was made for this mask, this `coarse`,
+        this number of near-nullspace vectors and this `setup`, the numeric phase runs on the values of this matrix (the smoother belongs to it: the cache
+        does not know it)'''
         from . import amg, device
         _, rowptr, colidx = self.triplet()
         k = None if nullspace is None else nullspace.shape[1]
-        if self._amg is None or self._amg[1] != coarse or self._amg[2] != k or not numpy.array_equal(self._amg[0], free):
-            self._amg = free.copy(), coarse, k, amg.symbolic(rowptr, colidx, None if mask is None else mask != 0, coarse, k)
+        if self._amg is None or self._amg[1] != coarse or self._amg[2] != k or self._amg[4] != setup or not numpy.array_equal(self._amg[0], free):
+            self._amg = free.copy(), coarse, k, amg.symbolic(rowptr, colidx, None if mask is None else mask != 0, coarse, k, setup=setup), setup
         if nullspace is not None:  # PCIe: a host array goes up once, n k doubles
             nullspace = nullspace.contiguous() if _is_tensor(nullspace) else device.to_dev(nullspace, 'float64')
         return amg.Hierarchy(self._amg[3], self.triplet()[0], sweeps, nullspace, smoother)

@@ -22,7 +22,8 @@
   * for the smoothed-aggregation AMG preconditioner (precon='amg'): the time of the symbolic and of the numeric phase of its setup, level sizes and operator
     complexity, one cycle against one masked product, and iterations, wall time and true residual of an AMG-CG solve (with the symbolic phase, and with it
     cached) beside the Jacobi-CG solve of the same system in the same process; for the vector matrices (elasticity96, p2vector32) all of that once more with
-    the rigid-body modes as the near-nullspace (preconargs=dict(nullspace=amg.rigid_body_modes(coords))),
+    the rigid-body modes as the near-nullspace (preconargs=dict(nullspace=amg.rigid_body_modes(coords))); with --amg-setup entry,block that part once per kind of
+    plan (preconargs' `setup`), each with the products of its plans, the peak of torch's allocator during its symbolic phase, and its own solve,
   * for the smoothers of that preconditioner (section 'smoother'; the rigid-body modes for the vector matrices), in one process and alternating: Jacobi with one
     (the default) and two sweeps and Chebyshev of degree 2 and 3 -- the numeric setup with the share of its Lanczos estimates, the bounds of every level, one
     cycle, and iterations and wall time of the solve to rtol = 1e-8 with the symbolic phase cached; with --eigratios 4,10,30 the Chebyshev degree-2 solve for
@@ -40,7 +41,7 @@
     the time is that call over 20).
 
 Usage: python tools/matrix_probe.py [--matrices poisson128,elasticity96,elasticity64,elasticity48,bilinear2048,bilinear1024,p2vector32,p2vector16] [--scale 1.0]
-[--sections spmv,cg,bicgstab,fgmres,minres,amg,smoother,algebra,columns] [--eigratios 4,10,30] [--eigsteps 5,10,20] [--out FILE]
+[--sections spmv,cg,bicgstab,fgmres,minres,amg,smoother,algebra,columns] [--amg-setup entry,block] [--eigratios 4,10,30] [--eigsteps 5,10,20] [--out FILE]
 (--scale shrinks every mesh for a quick look; --sections leaves parts out).  Not run by any test.'''
 import argparse
 import json
@@ -414,22 +415,34 @@ def probe_amg(A, free, mask, rhs_dev, res0, info, args):
     preconargs = {'amg': None, 'diag': None}
     if info['components'] > 1:
         B = device.to_dev(amg.rigid_body_modes(nodes_of(info)), 'float64')
-        rbm = out['rigid_body_modes'] = dict(k=B.shape[1])
-        try:
-            levels, rbm['symbolic_ms'] = clocked(lambda: amg.symbolic(rowptr, colidx, mask != 0, 256, B.shape[1]))
-            h, rbm['numeric_first_ms'] = clocked(lambda: amg.Hierarchy(levels, values, 1, B))
-            h, rbm['numeric_ms'] = clocked(lambda: amg.Hierarchy(levels, values, 1, B))
-            rbm['levels'] = [lv.nfree for lv in levels]
-            rbm['kinds'] = [lv.kind for lv in levels]
-            rbm['operator_complexity'] = sum(lv.colidx.numel() for lv in levels) / nnzs[0]
-            rbm['dropped_columns'] = [int((d.dinv == 0).sum()) for lv, d in zip(levels[1:], h.data[1:])]
-            t_cycle, = windows([lambda: h.apply(r, z)], args.window)
-            rbm['cycle'] = stats(t_cycle)
-            rbm['cycle_over_product'] = rbm['cycle']['us'] / out['masked_spmv']['us']
-            del h, levels
-            preconargs['amg_rbm'] = dict(nullspace=B)
-        except (matrix.MatrixError, RuntimeError) as e:  # (as above: recorded, not hidden)
-            rbm['error'] = f'{type(e).__name__}: {e}'
+        out['rigid_body_modes'] = dict(k=B.shape[1])
+        # --amg-setup entry,block: the setup once per kind of plan, side by side in this process; without it the default kind, as before
+        for setup in args.amg_setup or [None]:
+            rbm = out['rigid_body_modes'] if setup is None else out['rigid_body_modes'].setdefault(setup, {})
+            try:
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                before = torch.cuda.memory_allocated()
+                levels, rbm['symbolic_ms'] = clocked(lambda: amg.symbolic(rowptr, colidx, mask != 0, 256, B.shape[1], setup=setup))
+                rbm['symbolic_peak_bytes'] = torch.cuda.max_memory_allocated() - before  # (torch's allocator statistic: what the phase held at its peak, above what was there)
+                rbm['symbolic_kept_bytes'] = torch.cuda.memory_allocated() - before
+                rbm['setup'] = levels[0].setup
+                rbm['products_level0'] = {what: getattr(levels[0], what).nprod for what in ('at', 'ap', 'rap')} if levels[0].kind == 'coarsen' else None
+                rbm['products'] = [[getattr(lv, what).nprod for what in ('at', 'ap', 'rap')] for lv in levels if lv.kind == 'coarsen']
+                h, rbm['numeric_first_ms'] = clocked(lambda: amg.Hierarchy(levels, values, 1, B))
+                h, rbm['numeric_ms'] = clocked(lambda: amg.Hierarchy(levels, values, 1, B))
+                rbm['levels'] = [lv.nfree for lv in levels]
+                rbm['kinds'] = [lv.kind for lv in levels]
+                rbm['operator_complexity'] = sum(lv.colidx.numel() for lv in levels) / nnzs[0]
+                rbm['dropped_columns'] = [int((d.dinv == 0).sum()) for lv, d in zip(levels[1:], h.data[1:])]
+                t_cycle, = windows([lambda: h.apply(r, z)], args.window)
+                rbm['cycle'] = stats(t_cycle)
+                rbm['cycle_over_product'] = rbm['cycle']['us'] / out['masked_spmv']['us']
+                del h, levels
+                preconargs['amg_rbm' if setup is None else 'amg_rbm_' + setup] = dict(nullspace=B) if setup is None else dict(nullspace=B, setup=setup)
+            except (matrix.MatrixError, RuntimeError) as e:  # (as above: recorded, not hidden)
+                rbm['error'] = f'{type(e).__name__}: {e}'
+                levels = h = None  # (what the failed phase held goes back to the allocator before the next kind starts)
 
     def solve(name):
         try:
@@ -791,11 +804,15 @@ def main():
     ap.add_argument('--maxiter', type=int, default=20000)
     ap.add_argument('--no-host-solve', action='store_true', help='skip the host BiCGStab of the nonsymmetric twin (minutes for the large matrices)')
     ap.add_argument('--sections', default='spmv,cg,bicgstab,fgmres,minres,amg', help='the parts of the probe to run')
+    ap.add_argument('--amg-setup', default='', help="section 'amg', vector matrices: the kinds of plan to build the rigid-body hierarchy with, side by side, e.g. entry,block")
     ap.add_argument('--eigratios', default='', help="section 'smoother': the eigratio values of further Chebyshev degree-2 rows, e.g. 4,10,30")
     ap.add_argument('--eigsteps', default='', help="section 'smoother': the eigsteps values of further Chebyshev degree-2 rows, e.g. 5,10,20")
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     args.sections = args.sections.split(',')
+    args.amg_setup = [v for v in args.amg_setup.split(',') if v]
+    if set(args.amg_setup) - {'entry', 'block'}:
+        raise SystemExit(f"--amg-setup takes 'entry' and 'block', got {args.amg_setup}")
     args.eigratios = [float(v) for v in args.eigratios.split(',') if v]
     args.eigsteps = [int(v) for v in args.eigsteps.split(',') if v]
     import torch
