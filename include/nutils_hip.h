@@ -588,7 +588,8 @@ int nh_monomial(int64_t n, const double *values_dev, int nargs, const double *co
  * polynomials of ONE scalar field, c int s(x) u^k dV -> C_k[i1..ik] = coeff int s N_i1 .. N_ik dV: every permutation stored, entries sorted by
  * (i1, .., ik) lexicographically, exact zeros dropped -- the arrays evaluable.Monomial holds (evaluable.py:5693-5751) and nh_monomial consumes.
  * nh_factor_tensor builds the tensor and reports its length; nh_factor_fetch copies it into caller-owned buffers (values[nnz], indices[rank][nnz])
- * and releases the library's copy.  One build at a time (the single-stream contract of the scratch buffers). */
+ * and releases the library's copy.  One build at a time (the single-stream contract of the scratch buffers): a second build replaces the first, a fetch
+ * without a build fails.  A build without elements, or one whose entries all cancel, leaves a tensor of length 0: its fetch takes NULL buffers. */
 typedef struct {
   int64_t nelems;
   const int32_t *elist_dev;  /* optional element subset; scale_dev is indexed by list position */

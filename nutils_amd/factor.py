@@ -34,7 +34,10 @@ class Factored:
             if itg.rows or itg.cols:
                 raise ValueError('factor expects a scalar functional')
         self.name = name
-        grad = function.derivative(integral, name)
+        # c, f and K come from the element loops, which are not made for a sample without elements (an empty boundary group, a rank without elements: an empty
+        # element list reaches them as no list at all); such terms contribute nothing there.  The tensor builder below takes them: it returns no entries.
+        live = function.Integral([t for t in integral.terms if t[0].nlist])
+        grad = function.derivative(live, name)
         hess = function.derivative(grad, name)
         # the argument: a test / trial slot that carries the name, else the field of a polynomial factor (a pure value functional such as the integral of u^4)
         arg = next((a for _, itg, _ in integral.terms for a in (itg.test, itg.trial) if a is not None and a.name == name), None)
@@ -47,7 +50,7 @@ class Factored:
         self.size = int(numpy.prod(self.shape))
         zero = {name: numpy.zeros(self.shape)}
         # Taylor coefficients at u = 0, each evaluated ONCE with the element loop (evaluable.py:5846)
-        self.c = float(_sample.evaluate(integral, zero))
+        self.c = float(_sample.evaluate(live, zero)) if live.terms else 0.
         self.f = device.to_dev(numpy.asarray(_sample.evaluate(grad, zero)).ravel(), 'float64') if grad.terms else None
         self.K = []
         by_sample = {}

@@ -74,11 +74,12 @@ def test_rank3_tensor_built_on_the_device(golden):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('case', ['quartic2d', 'quartic3d_iso', 'boundary_cubic'])
+@pytest.mark.parametrize('case', ['quartic2d', 'quartic3d_iso', 'boundary_cubic', 'quartic1d', 'quartic2d_graded', 'quartic2d_coefficient'])
 def test_rank4_factor_equals_direct_integration(case):
     '''Quartic (double-well) functionals: the factored form -- tensors of rank 2, 3 and 4 built once, nh_monomial per evaluation -- against the
     element loop with pointwise polynomial coefficients, value and gradient; structural checks of the rank-4 tensor (symmetric under permutation of
-    its index arrays, keys strictly ascending).'''
+    its index arrays, keys strictly ascending).  quartic1d: one dimension; quartic2d_graded: elements of different sizes (and, as for every spline basis here,
+    several tables); quartic2d_coefficient: a coefficient function of the position in front of u^4, which reaches the builder as scale_dev.'''
     from nutils_amd import mesh, function, device
     rng = numpy.random.default_rng(3)
     if case == 'quartic3d_iso':
@@ -87,6 +88,12 @@ def test_rank4_factor_equals_direct_integration(case):
         verts = numpy.stack(numpy.meshgrid(numpy.arange(4.), numpy.arange(3.), numpy.arange(5.), indexing='ij'), -1).reshape(-1, 3) + rng.uniform(-.2, .2, (len(gb), 3))
         geom = gb @ verts
         btype, degree, gdeg = 'std', 1, 4
+    elif case == 'quartic1d':
+        domain, geom = mesh.rectilinear([numpy.linspace(0, 1, 8)])
+        btype, degree, gdeg = 'spline', 2, 8
+    elif case == 'quartic2d_graded':
+        domain, geom = mesh.rectilinear([numpy.array([0., .1, .3, .6, 1.]), numpy.array([0., .5, .7, 1.6, 2.])])
+        btype, degree, gdeg = 'spline', 2, 8
     else:
         domain, geom = mesh.rectilinear([numpy.linspace(0, 1, 6), numpy.linspace(0, 2, 5)])
         btype, degree, gdeg = 'spline', 2, 8
@@ -95,6 +102,9 @@ def test_rank4_factor_equals_direct_integration(case):
     dV = function.J(geom)
     if case == 'boundary_cubic':
         E = domain.integral((.5 * (function.grad(u, geom) * function.grad(u, geom)).sum(-1) + uu ** 2) * dV, degree=gdeg) + domain.boundary['left'].integral(uu ** 3 * dV, degree=gdeg)
+    elif case == 'quartic2d_coefficient':
+        kappa = function.PointFunc(lambda x: 1. + x[:, 0] * x[:, 1] - .5 * x[:, 1] ** 2, geom)  # changes sign inside the domain
+        E = domain.integral(((.5 * uu ** 3 - uu ** 2) + .5 * (function.grad(u, geom) * function.grad(u, geom)).sum(-1)) * dV, degree=gdeg) + domain.integral(kappa * uu ** 4 * dV, degree=gdeg)
     else:
         E = domain.integral((.25 * (uu ** 2 - 1.) ** 2 + .5 * (function.grad(u, geom) * function.grad(u, geom)).sum(-1) + .5 * uu ** 3) * dV, degree=gdeg)
     F = function.factor(E)
@@ -144,4 +154,31 @@ def test_factor_of_a_pure_value_functional():
     a, b = function.eval(F, u=uval), function.eval(E, u=uval)
     assert abs(a - b) <= 1e-12 * abs(b)
     ga, gb = function.eval(F.derivative('u'), u=uval), function.eval(function.derivative(E, 'u'), u=uval)
+    assert numpy.abs(ga - gb).max() <= 1e-12 * numpy.abs(gb).max()
+
+
+@pytest.mark.gpu
+def test_factor_with_a_cubic_term_on_a_boundary_without_elements():
+    '''int u^2 dV + int_Gamma u^3 dS with Gamma a boundary selection without elements.  The front end has no selection of boundary elements, so the smallest way
+    to a sample with nlist == 0 is the side's own topology with its element list emptied before its sample is made.  The builder is called with nelems == 0; it
+    must build (this raised "no tensor has been built" before), and no tensor of rank 3 remains.  The element loops behind c, f and K are not made for such a
+    sample (an empty list reaches them as no list: the scatter then sums local vectors that nothing wrote), so factor keeps its terms away from them: the
+    factored functional is that of the volume term alone.'''
+    from nutils_amd import mesh, function, topology
+    rng = numpy.random.default_rng(5)
+    domain, geom = mesh.rectilinear([numpy.linspace(0, 1, 5), numpy.linspace(0, 2, 4)])
+    u = domain.field('u', btype='spline', degree=2)
+    uu = function.value(u)
+    dV = function.J(geom)
+    gamma = topology.BoundaryTopology(domain, 0, 0)
+    gamma.elements, gamma.nelems = gamma.elements[:0], 0
+    assert gamma.sample('gauss', 6).nlist == 0
+    volume = domain.integral(uu ** 2 * dV, degree=6)
+    E = volume + gamma.integral(uu ** 3 * dV, degree=6)
+    F = function.factor(E)
+    assert F.T == []
+    uval = rng.normal(size=len(domain.basis('spline', degree=2)))
+    a, b = function.eval(F, u=uval), function.eval(volume, u=uval)
+    assert abs(a - b) <= 1e-12 * abs(b)
+    ga, gb = function.eval(F.derivative('u'), u=uval), function.eval(function.derivative(volume, 'u'), u=uval)
     assert numpy.abs(ga - gb).max() <= 1e-12 * numpy.abs(gb).max()
