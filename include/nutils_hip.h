@@ -115,6 +115,11 @@ int nh_pattern_info(const nh_pattern *p, int64_t *nnz_scalar, const int64_t **sr
  * launch: -1 none yet, 0 the tabulated any-element routine, 1 / 2 the sum-factorised routine for trilinear hexahedra at the 2 x 2 x 2 Gauss
  * points (recognised from the tables of the launch; 2: with a mass term) */
 int nh_pattern_fused_info(const nh_pattern *p, int *nblocks, int *rows_per_block, int64_t *nvisits, int *routine);
+/* kernel launches of the term-list entries (nh_assemble_terms, nh_assemble_terms_multi, nh_assemble_matrix_terms) since the library was loaded, per
+ * process and per kernel family: [0] k_terms, [1] k_terms_multi, [2] k_local_vterms2 (lane per element, residuals), [3] k_mterms, [4] k_local_terms,
+ * [5] k_local_terms2 (thread-per-element passes in front of the owner-side reduction).  Read only: nothing in the library depends on the counts; a test
+ * takes the difference around a call to see which family served it. */
+int nh_terms_launch_counts(int64_t counts[6]);
 /* row tasks of NH_MATRIX_FUSED for vector-valued blocks built for this pattern so far (nh_owner.hip): row blocks (0: none yet, or the plan does not
  * apply), node rows per block, element visits of all blocks, chunks of 64 contributions */
 int nh_pattern_owner_info(const nh_pattern *p, int *nblocks, int *rows_per_block, int64_t *nvisits, int64_t *nchunks);
@@ -339,7 +344,7 @@ int nh_assemble_terms(const nh_terms_args *args, void *stream);
 /* The term lists of several samples (the volume sample and the sides of the boundary of one residual: the reference fuses all loops of
  * equal length under one id, evaluable.py:6841-6895, but still runs one loop per sample) in ONE launch: every list gets a range of
  * workgroups.  Same result as `count` nh_assemble_terms calls (the outputs are accumulated either way); lists of another dimension than
- * the first and lists of more than 2^20 elements are launched on their own. */
+ * the first, lists of 2^14 elements and more (which may take the lane-per-element kernel) and lists beyond the eighth are launched on their own. */
 int nh_assemble_terms_multi(int count, const nh_terms_args *const *lists, void *stream);
 
 /* ---- fused bilinear-form assembly: all matrix terms of a block in ONE element loop ----------
@@ -360,7 +365,7 @@ typedef struct {
   int poly;                  /* pointwise polynomial factor, -1: none */
   const double *C_host;      /* [nct][S][ncr][S]: C (kind 0) or B (kinds 1, 2) */
   const double *L_host;      /* kind 2: [nct][S] */
-  const double *scale_dev;   /* [nelems][nq] or NULL */
+  const double *scale_dev;   /* [nelems][nq] or NULL; indexed like emap: by list position, with NH_MATRIX_EMAP_BY_ELEMENT by element */
   int qs_field_t, qs_field_r; /* as in nh_term */
   const double *qs_B_host;
 } nh_matrix_term;
@@ -386,7 +391,7 @@ typedef struct {
   int npolys;
   const nh_point_poly *polys;
   const nh_pattern *pattern; /* optional pattern handle: with NH_MATRIX_GATHER (| NH_MATRIX_STORE) in flags, scalar blocks on small uniform bases
-                                (2 x 2 ... 9 x 9 local matrices, at most two scalar fields on the test basis) are assembled by a thread-per-element
+                                (2 x 2 ... 9 x 9 local matrices, at most two scalar fields on the test basis: its tables AND its dof array) are assembled by a thread-per-element
                                 pass + the owner-side reduction of nh_assemble_matrix; other blocks ignore NH_MATRIX_GATHER */
 } nh_matrix_terms_args;
 

@@ -8,6 +8,7 @@
 // (evaluable.py:6773-6786, Inflate/Assemble scatter :3341-3495) for a list of terms, instead of one launch per term.
 #include "nh_common.h"
 #include <algorithm>
+#include <atomic>
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
@@ -28,6 +29,10 @@ constexpr int NBLK = 3;     // trial functions per lane in the contraction of th
 constexpr int MAXL = 8;    // term lists of one launch (nh_assemble_terms_multi)
 constexpr int TABARG = 256;  // doubles of the term table that fit the kernel arguments
 constexpr int TABPAD = 24;   // readable doubles behind them (records read whole, at the length of the longest kind)
+
+// launches per kernel family since the library was loaded (nh_terms_launch_counts): written where a launch is issued, read by nobody here
+enum { FAM_TERMS, FAM_TERMS_MULTI, FAM_LOCAL_VTERMS2, FAM_MTERMS, FAM_LOCAL_TERMS, FAM_LOCAL_TERMS2, NFAM };
+std::atomic<int64_t> launches[NFAM];
 
 __device__ __forceinline__ i64 boff(const BasisK &b, i64 e) { return b.off ? nh_g(b.off)[e] : e * (i64)b.nb; }
 __device__ __forceinline__ int bnb(const BasisK &b, i64 e) { return b.off ? (int)(nh_g(b.off)[e + 1] - nh_g(b.off)[e]) : b.nb; }
@@ -1247,7 +1252,7 @@ constexpr i64 LV2_MIN_ELEMS = 1 << 14;  // lists of this size get a launch of th
 #endif
 template <int ND, int NB, int NF>
 __global__ __launch_bounds__(64 * LV2_NW) __attribute__((amdgpu_waves_per_eu(NH_LV2_WPE, NH_LV2_WPE))) void k_local_vterms2(VTermsK p) {
-  constexpr int S = 1 + ND, NG = 1 << ND, NT = 64 * LV2_NW, UES = (NF * NB) | 1, RS = (2 * NB) | 1;
+  constexpr int S = 1 + ND, NT = 64 * LV2_NW, UES = (NF * NB) | 1, RS = (2 * NB) | 1;
   const double *tab = p.tabarg;
   extern __shared__ __attribute__((aligned(16))) double stab[];  // [ncls][NB][nq][S] tables | ue [64][UES], later the partial sums [LV2_NW - 1][64][RS]
   __shared__ i64 clsT[LT2_CLS];
@@ -1282,8 +1287,7 @@ __global__ __launch_bounds__(64 * LV2_NW) __attribute__((amdgpu_waves_per_eu(NH_
       for (int i = threadIdx.x; i < NB * p.nq * S; i += NT) stab[c * ntab + i] = p.test.T[clsT[c] * p.nq * S + i];
   const int slot = staged ? slotS[lane] : 0;
   __syncthreads();
-  const bool iso = p.geom.kind == NH_GEOM_ISO && p.geom.ngb == NG;
-  const bool perpoint = iso || p.geom.kind == NH_GEOM_TAB;
+  const bool perpoint = p.geom.kind != NH_GEOM_BOX;  // (isoparametric geometry of ANY order: a biquadratic map has another Jacobian at every point)
   double Jc[ND][ND], detc = 0;  // geometry that does not depend on the point (boxes): once
   if (!perpoint) geometry_at<ND>(p.geom, e, 0, p.nq, nullptr, Jc, detc, nullptr);
   const double *ue = ueS + lane * UES;
@@ -1556,7 +1560,7 @@ int local_terms(const nh_matrix_terms_args *a, const MTermsK &m, const std::vect
   if (!a->pattern || a->pattern->nelems != a->nelems || (a->elist_dev && (a->flags & NH_MATRIX_EMAP_BY_ELEMENT))) return NH_OK;
   if (a->nct != 1 || a->ncr != 1 || a->test.off_dev || a->trial.off_dev || !a->test.nb || !a->trial.nb || a->nfields > 2 || tab.size() > (size_t)TABARG) return NH_OK;
   for (int f = 0; f < a->nfields; ++f)
-    if (!m.fields[f].tsame || a->fields[f].ncomp != 1) return NH_OK;
+    if (!m.fields[f].tsame || a->fields[f].basis.dofs_dev != a->test.dofs_dev || a->fields[f].ncomp != 1) return NH_OK;  // (the kernels gather the field coefficients through the test dofs)
   LTermsK p;
   p.nelems = a->nelems, p.elist = a->elist_dev, p.nq = a->nq, p.weights = a->weights_dev;
   p.geom = m.geom, p.test = m.test, p.trial = m.trial;
@@ -1601,6 +1605,7 @@ int local_terms(const nh_matrix_terms_args *a, const MTermsK &m, const std::vect
   do {                                                                                                                                                   \
     NH_CHECK_HIP(hipFuncSetAttribute((const void *)k_local_terms2<ND, NBT, NBR, NBK, NF, ISO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));   \
     hipLaunchKernelGGL((k_local_terms2<ND, NBT, NBR, NBK, NF, ISO>), grid2, block2, lds2, s, p);                                                          \
+    ++launches[FAM_LOCAL_TERMS2];                                                                                                                         \
   } while (0)
 #define LT2(ND, NBT, NBR, NBK, NF)             \
   do {                                         \
@@ -1624,6 +1629,7 @@ int local_terms(const nh_matrix_terms_args *a, const MTermsK &m, const std::vect
     if (a->nfields == 0) hipLaunchKernelGGL((k_local_terms<ND, NBT, NBR, NBT, 0>), grid, block, ldst, s, p);      \
     else if (a->nfields == 1) hipLaunchKernelGGL((k_local_terms<ND, NBT, NBR, NBT, 1>), grid, block, ldst, s, p); \
     else hipLaunchKernelGGL((k_local_terms<ND, NBT, NBR, NBT, 2>), grid, block, ldst, s, p);                      \
+    ++launches[FAM_LOCAL_TERMS];                                                                          \
   } while (0)
     switch (key) {
       case 10202: LT(1, 2, 2); break;
@@ -1684,6 +1690,7 @@ int local_vterms(const nh_terms_args *a, const TermsK &m, const std::vector<doub
   do {                                                                                                                                   \
     NH_CHECK_HIP(hipFuncSetAttribute((const void *)k_local_vterms2<ND, NB, NF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));  \
     hipLaunchKernelGGL((k_local_vterms2<ND, NB, NF>), grid2, block2, lds2, s, p);                                                         \
+    ++launches[FAM_LOCAL_VTERMS2];                                                                                                        \
   } while (0)
 #define LV2(ND, NB)                             \
   do {                                          \
@@ -1853,6 +1860,12 @@ int list_slot(const std::vector<char> &image, ListSlot **out, bool *hit) {
 
 }  // namespace
 
+extern "C" int nh_terms_launch_counts(int64_t counts[6]) {
+  NH_REQUIRE(counts, "nh_terms_launch_counts: NULL argument");
+  for (int i = 0; i < NFAM; ++i) counts[i] = launches[i].load();
+  return NH_OK;
+}
+
 extern "C" int nh_assemble_terms(const nh_terms_args *a, void *stream) {
   TermsK p;
   std::vector<double> tab;
@@ -1874,6 +1887,7 @@ extern "C" int nh_assemble_terms(const nh_terms_args *a, void *stream) {
   do {                                                                                                                      \
     NH_CHECK_HIP(hipFuncSetAttribute((const void *)k_terms<ND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));     \
     hipLaunchKernelGGL(k_terms<ND>, grid, block, lds, s, p);                                                                \
+    ++launches[FAM_TERMS];                                                                                                  \
   } while (0)
   if (a->ndims == 1) LAUNCH(1);
   if (a->ndims == 2) LAUNCH(2);
@@ -1957,6 +1971,7 @@ extern "C" int nh_assemble_terms_multi(int count, const nh_terms_args *const *li
   do {                                                                                                                            \
     NH_CHECK_HIP(hipFuncSetAttribute((const void *)k_terms_multi<ND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));     \
     hipLaunchKernelGGL(k_terms_multi<ND>, grid, block, lds, s, (const TermsK *)sl->dev, m);                                       \
+    ++launches[FAM_TERMS_MULTI];                                                                                                  \
   } while (0)
   if (ndims == 1) LAUNCH(1);
   if (ndims == 2) LAUNCH(2);
@@ -2084,6 +2099,7 @@ extern "C" int nh_assemble_matrix_terms(const nh_matrix_terms_args *a, void *str
   do {                                                                                                                      \
     NH_CHECK_HIP(hipFuncSetAttribute((const void *)k_mterms<ND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));    \
     hipLaunchKernelGGL(k_mterms<ND>, grid, block, lds, s, p);                                                               \
+    ++launches[FAM_MTERMS];                                                                                                 \
   } while (0)
   if (a->ndims == 1) LAUNCH(1);
   if (a->ndims == 2) LAUNCH(2);

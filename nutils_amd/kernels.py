@@ -348,6 +348,16 @@ def assemble_terms_multi(lists):
     _lib.call('nh_assemble_terms_multi', len(args), ptrs, device.stream())
 
 
+TERMS_FAMILIES = ('k_terms', 'k_terms_multi', 'k_local_vterms2', 'k_mterms', 'k_local_terms', 'k_local_terms2')
+
+
+def terms_launch_counts():
+    '''{kernel family: launches since the library was loaded} of the term-list entries (nh_terms_launch_counts).'''
+    counts = (ctypes.c_int64 * len(TERMS_FAMILIES))()
+    _lib.call('nh_terms_launch_counts', counts)
+    return dict(zip(TERMS_FAMILIES, counts))
+
+
 def _qs(qs, S):
     '''term option qs = (B [S][S], field_t, field_r): point factor U_t . B . U_r'''
     if qs is None:
