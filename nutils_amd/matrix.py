@@ -586,14 +586,17 @@ class HipMatrix:
         if solver == 'fgmres' and not (isinstance(restart, (int, numpy.integer)) and not isinstance(restart, bool) and restart >= 1):
             raise MatrixError(f'fgmres: restart must be an integer of at least 1, got {restart!r}')
         free, lhs = constraints(ncols, _host(constrain), _host(lhs0))
-        args = (rhs, free, lhs, atol, rtol, precon, int(free.sum()) if maxiter is None else int(maxiter), max(1, int(check)), on_device)
-        if solver == 'cg':
-            return self._cg(*args, preconargs)
-        if solver == 'bicgstab':
-            return self._bicgstab(*args)
-        if solver == 'minres':
-            return self._minres(*args)
-        return self._fgmres(*args, int(restart))
+        from . import krylov
+        maxiter, check = int(free.sum()) if maxiter is None else int(maxiter), max(1, int(check))
+        args = self, rhs, free, lhs, precon, on_device
+        rec = (krylov.Cg(*args, preconargs) if solver == 'cg' else krylov.Fgmres(*args, int(restart)) if solver == 'fgmres'
+               else krylov.Bicgstab(*args) if solver == 'bicgstab' else krylov.Minres(*args))
+        try:
+            return krylov.solve(rec, atol, rtol, maxiter, check)
+        finally:
+            self.iterations = rec.iterations
+            if solver == 'cg':
+                self.cg_iterations = rec.iterations
 
     def solve_leniently(self, *args, **kwargs):
         '''`solve` that returns the vector reached instead of raising ToleranceNotReached'''
@@ -734,167 +737,6 @@ class HipMatrix:
         if nullspace is not None:  # PCIe: a host array goes up once, n k doubles
             nullspace = nullspace.contiguous() if _is_tensor(nullspace) else device.to_dev(nullspace, 'float64')
         return amg.Hierarchy(self._amg[3], self.triplet()[0], sweeps, nullspace, smoother)
-
-    def _cg(self, rhs, free, lhs, atol, rtol, precon, maxiter, check, on_device, preconargs=None):
-        from . import device, kernels
-        n = self.shape[0]
-        values, rowptr, colidx = self.triplet()
-        mask, x, b, dinv = self._krylov_setup(rhs, free, lhs, None if precon == 'amg' else precon, on_device)
-        r, p, q = (device.empty(n, 'float64') for _ in range(3))
-        csr = dict(rowmask=mask, x=x, r=r, p=p, q=q, col32=self._columns(), lanes=self.lanes)
-        if precon == 'amg':  # z = M r is a V-cycle (nh_amg.hip); the loop below is the same
-            hierarchy = self._amg_hierarchy(free, mask, *preconargs)
-            z, work = device.empty(n, 'float64'), kernels.pcg_work()
-            init = lambda: kernels.pcg_init(hierarchy.handle, r, z, p, work)
-            iterate = lambda steps: kernels.pcg_iterate(values, rowptr, colidx, self._ncols, amg=hierarchy.handle, z=z, work=work, niter=steps, **csr)
-        else:
-            work = kernels.cg_work()
-            init = lambda: kernels.cg_init(dinv, r, p, work)
-            iterate = lambda steps: kernels.cg_iterate(values, rowptr, colidx, self._ncols, dinv=dinv, work=work, niter=steps, **csr)
-        result = (lambda: x) if on_device else (lambda: device.to_host(x))
-        stop_rr, it = None, 0
-        while True:
-            self.cg_iterations = self.iterations = it  # (of the last solve, for whoever wants to know)
-            self.spmv(x, alpha=-1., beta=1., b=b, rowmask=mask, y=r)  # the true residual, mask(rhs - A x)
-            init()
-            rr, _ = work[:2].tolist()
-            if stop_rr is None:
-                stop_rr = max(atol, rtol * rr ** .5) ** 2  # (the device compares r . r with this number, and so does the host)
-            if not numpy.isfinite(rr):
-                raise MatrixError('cg: non-finite residual')
-            if rr <= stop_rr:
-                return result()
-            if it >= maxiter:
-                raise ToleranceNotReached(result())
-            kernels.cg_stop(work, stop_rr)  # (the iterations enqueued past convergence idle: their r . z would underflow before r . r, a false breakdown)
-            while it < maxiter:
-                steps = min(check, maxiter - it)
-                iterate(steps)
-                it += steps
-                rr, flag = work[:2].tolist()
-                if flag:
-                    raise MatrixError('cg: matrix is not positive definite')
-                if not numpy.isfinite(rr):
-                    raise MatrixError('cg: non-finite residual')
-                if rr <= stop_rr:
-                    break
-
-    def _bicgstab(self, rhs, free, lhs, atol, rtol, precon, maxiter, check, on_device):
-        from . import device, kernels
-        n = self.shape[0]
-        values, rowptr, colidx = self.triplet()
-        mask, x, b, dinv = self._krylov_setup(rhs, free, lhs, precon, on_device)
-        r, rhat, p, v, s, t = (device.empty(n, 'float64') for _ in range(6))
-        phat, shat = (device.empty(n, 'float64') for _ in range(2)) if dinv is not None else (None, None)
-        work = kernels.bicgstab_work()
-        result = (lambda: x) if on_device else (lambda: device.to_host(x))
-        stop_rr, it = None, 0
-        while True:  # a start: from the true residual, with a fresh shadow residual
-            self.iterations = it
-            self.spmv(x, alpha=-1., beta=1., b=b, rowmask=mask, y=r)  # mask(rhs - A x)
-            kernels.bicgstab_init(dinv, r, rhat, p, phat, work)
-            rr = work[:1].item()
-            if stop_rr is None:
-                stop_rr = max(atol, rtol * rr ** .5) ** 2  # (the device compares r . r with this number, and so does the host)
-            if not numpy.isfinite(rr):
-                raise MatrixError('bicgstab: non-finite residual')
-            if rr <= stop_rr:
-                return result()
-            if it >= maxiter:
-                raise ToleranceNotReached(result())
-            start = it
-            while it < maxiter:
-                kernels.bicgstab_iterate(values, rowptr, colidx, self._ncols, rowmask=mask, dinv=dinv, x=x, r=r, rhat=rhat, p=p, v=v, s=s, t=t, phat=phat, shat=shat,
-                                         work=work, stop_rr=stop_rr, niter=min(check, maxiter - it), col32=self._columns(), lanes=self.lanes)
-                rr, flag, moved = work[:3].tolist()
-                self.iterations = it = start + int(moved)  # (the device counts the iterations that moved x: exact, not a multiple of `check`)
-                if flag:
-                    if not moved:
-                        raise MatrixError('bicgstab: breakdown')
-                    break  # restart from where the recurrence got to
-                if not numpy.isfinite(rr):
-                    raise MatrixError('bicgstab: non-finite residual')
-                if rr <= stop_rr:
-                    break
-
-    def _minres(self, rhs, free, lhs, atol, rtol, precon, maxiter, check, on_device):
-        from . import device, kernels
-        n = self.shape[0]
-        values, rowptr, colidx = self.triplet()
-        mask, x, b, dinv = self._krylov_setup(rhs, free, lhs, precon, on_device)
-        if dinv is not None:
-            dinv = dinv.abs()  # (the preconditioner of MINRES is positive definite: 1 / |diag|)
-        r, r1, r2, v, q, w1, w2 = (device.empty(n, 'float64') for _ in range(7))
-        work = kernels.minres_work()
-        result = (lambda: x) if on_device else (lambda: device.to_host(x))
-        stop_rr, it = None, 0
-        while True:  # a start: from the true residual
-            self.iterations = it
-            self.spmv(x, alpha=-1., beta=1., b=b, rowmask=mask, y=r)  # mask(rhs - A x)
-            kernels.minres_init(dinv, r, r1, r2, v, w1, w2, work)
-            rr = work[:1].item()
-            if stop_rr is None:
-                stop_rr = max(atol, rtol * rr ** .5) ** 2  # (the device compares r . r with this number, and so does the host)
-            if not numpy.isfinite(rr):
-                raise MatrixError('minres: non-finite residual')
-            if rr <= stop_rr:
-                return result()
-            if it >= maxiter:
-                raise ToleranceNotReached(result())
-            start = it
-            while it < maxiter:
-                kernels.minres_iterate(values, rowptr, colidx, self._ncols, rowmask=mask, dinv=dinv, x=x, r=r, r1=r1, r2=r2, v=v, q=q, w1=w1, w2=w2, work=work,
-                                       stop_rr=stop_rr, niter=min(check, maxiter - it), col32=self._columns(), lanes=self.lanes)
-                rr, flag, moved = work[:3].tolist()
-                self.iterations = it = start + int(moved)  # (the device counts the iterations that moved x: exact, not a multiple of `check`)
-                if flag:
-                    if not moved:
-                        raise MatrixError('minres: breakdown')
-                    break  # restart from where the recurrence got to
-                if not numpy.isfinite(rr):
-                    raise MatrixError('minres: non-finite residual')
-                if rr <= stop_rr:
-                    break
-
-    def _fgmres(self, rhs, free, lhs, atol, rtol, precon, maxiter, check, on_device, restart):
-        from . import device, kernels
-        n = self.shape[0]
-        values, rowptr, colidx = self.triplet()
-        mask, x, b, dinv = self._krylov_setup(rhs, free, lhs, precon, on_device)
-        m = max(1, min(restart, int(free.sum())))  # (a Krylov space has no more dimensions than there are free dofs)
-        r, z, w = (device.empty(n, 'float64') for _ in range(3))
-        V = device.empty((m + 1) * n, 'float64')
-        work = kernels.gmres_work(m)
-        result = (lambda: x) if on_device else (lambda: device.to_host(x))
-        stop_rr, it, since, rr_start = None, 0, None, None  # since: cycles finished since one ended on a vanished direction (0: the last one did)
-        while True:  # a cycle: from the true residual
-            self.iterations = it
-            self.spmv(x, alpha=-1., beta=1., b=b, rowmask=mask, y=r)  # mask(rhs - A x)
-            kernels.gmres_init(dinv, r, V, z, work, restart=m)
-            rr = work[:1].item()
-            if stop_rr is None:
-                stop_rr = max(atol, rtol * rr ** .5) ** 2  # (the device compares its estimate with this number, and so does the host)
-            if not numpy.isfinite(rr):
-                raise MatrixError('fgmres: non-finite residual')
-            if rr <= stop_rr:
-                return result()
-            if since in (0, 1) and not rr < rr_start:
-                # A direction has vanished: the Krylov space of that start was exhausted, which for a nonsingular matrix means the update solved the system to
-                # rounding.  If that cycle got nowhere, or the next one on what rounding left of the residual (on diag(1, 0) it finds a direction of the size of
-                # a rounding in x, and no flag), the matrix is singular.  Later cycles that stagnate are restarted GMRES stagnating: they run to maxiter.
-                raise MatrixError('fgmres: singular matrix')
-            if it >= maxiter:
-                raise ToleranceNotReached(result())
-            start, rr_start = it, rr
-            while it < maxiter:
-                kernels.gmres_iterate(values, rowptr, colidx, self._ncols, rowmask=mask, dinv=dinv, V=V, z=z, w=w, work=work, restart=m, stop_rr=stop_rr,
-                                      niter=min(check, maxiter - it), col32=self._columns(), lanes=self.lanes)
-                est, flag, steps = work[:3].tolist()
-                self.iterations = it = start + int(steps)  # (the device counts the columns it took: exact, not a multiple of `check`)
-                if flag or est <= stop_rr or steps >= m:
-                    break
-            since = 0 if flag else None if since is None else since + 1
-            kernels.gmres_update(dinv, V, x, work, restart=m)
 
 
 class _HipBackend:
