@@ -891,7 +891,15 @@ int nh_gmres_update(int64_t n, int restart, const double *dinv_dev, const double
  * r -= alpha q, partials of r . r; z = M r; partials of r . z; beta, p = z + beta p.  work_dev: nh_pcg_work_doubles() doubles; work[0 .. 2] are r . r, the
  * breakdown flag and the stopping bound with the meaning they have in nh_cg_*: once r . r <= work[2] no iteration moves x, r or p or raises the flag; a
  * p . q or r . z that is not a positive finite number while r . r > work[2] raises it and freezes the vectors.  nh_pcg_init forms z = M r, p = z and the
- * first r . z, r . r from a given r, and clears flag and bound. */
+ * first r . z, r . r from a given r, and clears flag and bound.
+ * nh_fgmres_iterate: flexible GMRES for ANY square A with that cycle as its preconditioner, on the vectors, the work array and the rules of nh_gmres_*: the
+ * cycle is started by nh_gmres_init with dinv_dev NULL (v_0 = r / |r|, z a copy of it) and ended by nh_gmres_update(n, restart, NULL, Z_dev, x, work), which is
+ * x += Z y.  Step j of the niter it enqueues: t = M z (the cycle of nh_amg_apply; the hierarchy may have been built on other values than A's: any linear or
+ * nonlinear M will do, which is what "flexible" means); Z_j = t; w = mask(A t); the Gram-Schmidt passes, the scalars and v_(j+1) = w / h_(j+1,j), z = v_(j+1) of
+ * nh_gmres_iterate: ten launches and a cycle.  V_dev: restart + 1 vectors of n doubles, Z_dev: restart; z_dev, t_dev, w_dev: n doubles, z_dev and t_dev distinct:
+ * 2 restart + 1 basis vectors in all.  A step that finds the cycle stopped (work[0] <= stop_rr, restart columns taken, a direction vanished) leaves V, Z and the
+ * work array alone; its V-cycle still runs, into t.  NULL hierarchy or vectors, a hierarchy of another size, restart < 1, negative niter or stop_rr and a
+ * matrix that is not square are NH_EINVAL before a launch. */
 typedef struct nh_amg nh_amg;
 enum { NH_AMG_COARSEN = 0, NH_AMG_DENSE = 1, NH_AMG_DIAGONAL = 2 };
 enum { NH_AMG_JACOBI = 0, NH_AMG_CHEBYSHEV = 1 };
@@ -930,6 +938,8 @@ int64_t nh_pcg_work_doubles(void);
 int nh_pcg_init(int64_t n, const nh_amg *amg, const double *r_dev, double *z_dev, double *p_dev, double *work_dev, void *stream);
 int nh_pcg_iterate(const nh_csr *A, const unsigned char *rowmask_dev, const nh_amg *amg, double *x_dev, double *r_dev, double *z_dev, double *p_dev, double *q_dev,
                    double *work_dev, int niter, void *stream);
+int nh_fgmres_iterate(const nh_csr *A, const unsigned char *rowmask_dev, const nh_amg *amg, double *V_dev, double *Z_dev, double *z_dev, double *t_dev, double *w_dev,
+                      double *work_dev, int restart, double stop_rr, int niter, void *stream);
 
 #ifdef __cplusplus
 }

@@ -244,6 +244,7 @@ SIGNATURES = {
     'nh_pcg_work_doubles': (c_i64, []),
     'nh_pcg_init': (ctypes.c_int, [c_i64, vp, vp, vp, vp, vp, vp]),
     'nh_pcg_iterate': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int, vp]),
+    'nh_fgmres_iterate': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, vp]),
 }
 
 _lib = None

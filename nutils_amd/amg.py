@@ -1,4 +1,5 @@
-'''Smoothed-aggregation algebraic multigrid for ``HipMatrix.solve(solver='cg', precon='amg')``.
+'''Smoothed-aggregation algebraic multigrid for ``HipMatrix.solve(solver='cg', precon='amg')`` and, as an object of ``HipMatrix.getprecon`` (``Preconditioner``),
+for ``solve(solver='cg' | 'fgmres', precon=M)``.
 
 Two phases.  ``symbolic`` reads the pattern and the constraint mask only and is written with torch tensor operations that run wherever their inputs
 live (on the device in a solve, on CPU tensors in the tests): the aggregates, the CSR patterns of the prolongator P, the restriction R = P^T and the
@@ -21,8 +22,9 @@ aggregation  a distance-2 maximal independent set by Luby rounds on the graph of
              ascending root index.  All of it is max-reductions: a pure function of pattern and mask.
 prolongator  T[i, agg(i)] = 1 on free dofs; P = T - omega diag(dinv) A_f T (zero rows on constrained dofs), R = P^T stored as a CSR of its own,
              A_c = P^T A_f P.  P is held on the pattern of A_f T, which contains that of T wherever a free row has its diagonal entry.
-termination  a level with at most ``coarse`` free dofs is solved densely (numpy.linalg.pinv(A_c, hermitian=True)); a level whose graph has no edges is
-             solved by z = dinv b; any other level is coarsened.
+termination  a level with at most ``coarse`` free dofs is solved densely (numpy.linalg.pinv(A_c, hermitian=True); for a hierarchy made with symmetric=False,
+             whose matrix need not be symmetric, the general numpy.linalg.pinv(A_c)); a level whose graph has no edges is solved by z = dinv b; any other
+             level is coarsened.
 cycle        V(sweeps, sweeps): x = omega dinv b, further sweeps x += omega dinv (b - A x), r = b - A x, x += P cycle(R r), `sweeps` sweeps more.  Equal
              pre- and post-smoothing with omega < 2 / rho keeps the cycle symmetric positive definite, which CG needs.
 chebyshev    ``smoother='chebyshev'`` (``degree=2, eigsteps=10, eigratio=10.``) replaces the Jacobi sweeps of every coarsened level by a Chebyshev polynomial in
@@ -594,13 +596,17 @@ class Hierarchy:
     tensor [n x k], for levels of ``symbolic(..., nullspace=k)``; a coarsened level then keeps its own as B, the values of T as q [n x k], and hands the
     triangles of the aggregates' QR on as the B of the next.  `smoother`: None (Jacobi) or the dict of `split_smoother`; a coarsened level then also keeps the
     Lanczos estimate theta of the largest eigenvalue of D^-1 A_f with the steps it took (eigsteps), ub, lb (host numbers), the coefficients of its polynomial
-    (coef: 2 degree doubles on the device) and the vector d of the recurrence.  The estimate costs one look at the device per level: 2 eigsteps + 1 doubles.'''
+    (coef: 2 degree doubles on the device) and the vector d of the recurrence.  The estimate costs one look at the device per level: 2 eigsteps + 1 doubles.
+    `symmetric=False`: the matrix need not be symmetric (its pattern must be, structurally): the dense level's inverse is then the general pseudo-inverse, and
+    a Chebyshev smoother, whose bound is a Lanczos estimate, is refused; every other step of the setup reads no symmetry.'''
 
-    def __init__(self, levels, values, sweeps=1, nullspace=None, smoother=None):
+    def __init__(self, levels, values, sweeps=1, nullspace=None, smoother=None, symmetric=True):
         from . import device, kernels
         from .matrix import MatrixError, spmv_lanes
         torch = _torch()
         self.levels, self.data = levels, []
+        if smoother is not None and not symmetric:
+            raise MatrixError("amg: smoother='chebyshev' takes its bound from a Lanczos estimate, which needs a symmetric matrix; with symmetric=False the smoother is 'jacobi'")
         descriptions = []
         B, nk = nullspace, levels[0].k
         if (nk is None) != (B is None) or (B is not None and tuple(B.shape) != (levels[0].n, nk)):
@@ -624,7 +630,8 @@ class Hierarchy:
                 dense = numpy.zeros((lv.nfree, lv.nfree))
                 numpy.add.at(dense, (device.to_host(lv.drow), device.to_host(lv.dcol)), device.to_host(values[lv.dk]))
                 d.idx = lv.idx32
-                d.ainv = device.to_dev(numpy.linalg.pinv(dense, hermitian=True).ravel(), 'float64') if lv.nfree else None
+                # (a symmetric matrix takes the pseudo-inverse from its eigenvalues, as ever; that of a matrix that need not be comes from its singular values)
+                d.ainv = device.to_dev(numpy.linalg.pinv(dense, hermitian=bool(symmetric)).ravel(), 'float64') if lv.nfree else None
                 desc.update(kind='dense', ndense=lv.nfree, Ainv=d.ainv, idx=d.idx)
                 break
             if lv.kind == 'diagonal':
@@ -665,3 +672,31 @@ class Hierarchy:
     def apply(self, r, z=None):
         '''z = M r, one cycle (nh_amg_apply)'''
         return self.handle.apply(r, z)
+
+
+class Preconditioner:
+    '''What ``HipMatrix.getprecon`` returns (the reference's Matrix.getprecon, matrix/_base.py): a preconditioner built once, applied by `M(r)` and taken by
+    ``HipMatrix.solve(precon=M)`` in place of a name, on the matrix it was built on or on any other of the same shape, pattern and free mask -- the next Newton
+    step's, say.  `kind`: 'amg' (`hierarchy`: the ``Hierarchy``, whose handle, level values and scratch vectors live as long as this object) or 'diag' (`dinv`:
+    the inverse diagonal, 0 on constrained rows); `shape`: of the matrix; `free`: the host bool mask of the free dofs it was built for; `mask`: the same on the
+    device (None: all free); `values`: the value tensor it was built on; `symmetric`: whether the operator may precondition conjugate gradients.'''
+
+    def __init__(self, kind, shape, free, symmetric, values, mask, *, hierarchy=None, dinv=None):
+        self.kind, self.shape, self.free, self.symmetric, self.values, self.mask = kind, tuple(shape), free, bool(symmetric), values, mask
+        self.hierarchy, self.dinv = hierarchy, dinv
+
+    def __repr__(self):
+        return f'<{self.kind!r} preconditioner of a {self.shape[0]}x{self.shape[1]} HipMatrix, {int(self.free.sum())} free dofs, symmetric={self.symmetric}>'
+
+    def __call__(self, r):
+        '''z = M r, one application: a numpy vector gives a numpy vector, a float64 device tensor a device tensor.  'amg': one V-cycle (``Hierarchy.apply``) on r
+        as it is given; 'diag': dinv r.'''
+        from . import device
+        tensor = type(r).__module__.split('.')[0] == 'torch'
+        if not tensor:
+            r = numpy.asarray(r, dtype=float)
+        if r.ndim != 1 or r.shape[0] != self.shape[0] or (tensor and str(r.dtype) != 'torch.float64'):
+            raise _error()(f'a preconditioner of a {self.shape[0]}x{self.shape[1]} matrix takes a float64 vector of {self.shape[0]} entries, got {tuple(r.shape)} {r.dtype}')
+        rdev = r.contiguous() if tensor else device.to_dev(r, 'float64')
+        z = self.hierarchy.apply(rdev) if self.kind == 'amg' else self.dinv * rdev
+        return z if tensor else device.to_host(z)

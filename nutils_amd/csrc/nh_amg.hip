@@ -22,6 +22,8 @@
 //   * k_dense: z = Ainv b for the coarsest level, one workgroup, a wave per row, lanes over the columns.
 //   * the cycle (amg_cycle) is a host loop over the level descriptions that enqueues those kernels and nh_csr_spmv (residual, restriction,
 //     prolongate-and-add); with one sweep that is five launches per level and one for the coarsest.
+//   * nh_fgmres_iterate: flexible GMRES with the cycle as its preconditioner: t = M z by amg_cycle, then the Arnoldi step of nh_csr.hip from the product input t
+//     (nh_gmres_step_from), which keeps t as a column of Z.  No kernel of its own here.
 //   * k_pcg_*: CG with z = M r handed in.  An iteration: q = mask(A p) with the partials of p . q (the DOT = 1 product of nh_csr.hip); update (alpha, x,
 //     r, partials of r . r); the cycle; partials of r . z; direction (beta, p = z + beta p).  The cell discipline is that of k_cg_update / k_cg_direction.
 #include "nh_common.h"
@@ -876,6 +878,24 @@ int nh_pcg_iterate(const nh_csr *A, const unsigned char *rowmask_dev, const nh_a
     NH_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_pcg_direction, dim3(grid), dim3(WG), 0, s, n, (int)grid, work_dev, (const double *)z_dev, p_dev);
     NH_LAUNCH_CHECK();
+  }
+  return NH_OK;
+}
+
+int nh_fgmres_iterate(const nh_csr *A, const unsigned char *rowmask_dev, const nh_amg *amg, double *V_dev, double *Z_dev, double *z_dev, double *t_dev, double *w_dev,
+                      double *work_dev, int restart, double stop_rr, int niter, void *stream) {
+  if (int rc = check_csr("nh_fgmres_iterate", A)) return rc;
+  NH_REQUIRE(A->nrows == A->ncols, "nh_fgmres_iterate: the matrix must be square (got %lld x %lld)", (long long)A->nrows, (long long)A->ncols);
+  NH_REQUIRE(restart >= 1, "nh_fgmres_iterate: restart must be at least 1 (got %d)", restart);
+  NH_REQUIRE(niter >= 0, "nh_fgmres_iterate: negative iteration count");
+  NH_REQUIRE(stop_rr >= 0., "nh_fgmres_iterate: the bound on r . r must not be negative");
+  NH_REQUIRE(amg && amg->levels[0].A.nrows == A->nrows, "nh_fgmres_iterate: NULL hierarchy, or one of another size");
+  NH_REQUIRE(work_dev && (!A->nrows || (V_dev && Z_dev && z_dev && t_dev && w_dev && z_dev != t_dev)), "nh_fgmres_iterate: NULL vector, or the cycle's result is its argument");
+  if (!A->nrows) return NH_OK;
+  hipStream_t s = nh_stream(stream);
+  for (int it = 0; it < niter; ++it) {
+    if (int rc = amg_cycle(amg, 0, z_dev, t_dev, s)) return rc;  // (also past a stop: the cycle reads no status, its result then goes nowhere)
+    if (int rc = nh_gmres_step_from(A, rowmask_dev, t_dev, Z_dev, V_dev, z_dev, w_dev, work_dev, restart, stop_rr, s)) return rc;
   }
   return NH_OK;
 }

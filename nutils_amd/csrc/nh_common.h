@@ -39,6 +39,10 @@ int nh_scan_exclusive64(const i64 *in_dev, i64 *out_dev, i64 n, hipStream_t stre
 // nh_csr.hip, for the solvers of other files: q = mask(A p) and the per-workgroup partials of p . q (the product of a CG step); *npartials: how many were written
 int nh_csr_spmv_pq(const nh_csr *A, const double *p_dev, const unsigned char *rowmask_dev, double *q_dev, double *partial_dev, int max_partials, int *npartials,
                    hipStream_t stream);
+// nh_csr.hip, for nh_fgmres_iterate: the rest of an Arnoldi step of nh_gmres_* from a given product input t = M z, without a diagonal: t is kept as column
+// work[2] of Z, then w = mask(A t), the two Gram-Schmidt passes, the scalars, v_(j+1) = w / h_(j+1,j) and z = v_(j+1); ten launches that idle once the cycle has a status
+int nh_gmres_step_from(const nh_csr *A, const unsigned char *rowmask_dev, const double *t_dev, double *Z_dev, double *V_dev, double *z_dev, double *w_dev, double *work_dev,
+                       int restart, double stop_rr, hipStream_t stream);
 
 // geometry / basis structs are passed by value to kernels
 struct GeomK {

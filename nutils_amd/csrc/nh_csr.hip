@@ -889,6 +889,14 @@ __global__ __launch_bounds__(WG) void k_gmres_xupdate(i64 n, int m, const double
     st<VW>(x + i, xi);
   }
 }
+
+// Z_count = t: the column of the flexible method, what the preconditioner returned for v_count (count = G_COUNT, as the step that follows reads it)
+template <int VW>
+__global__ __launch_bounds__(WG) void k_gmres_keep(i64 n, int m, const double *__restrict__ t, double *__restrict__ Z, const double *__restrict__ work) {
+  if (work[G_ST] != 0.) return;
+  double *zc = Z + (i64)gmres_column(work, m) * n;
+  NH_GS_ROWS(i) st<VW>(zc + i, ld<VW>(t + i));
+}
 #undef NH_GS_ROWS
 
 // what a product leaves besides y: nothing (partial == NULL), the partials of x . y (w == NULL), or those of w . y and y . y; with a skip cell and no
@@ -971,32 +979,44 @@ bool gs_pairs(i64 n, std::initializer_list<const void *> vectors) {
 }
 unsigned gs_grid(i64 n, int vw) { return (unsigned)std::min<i64>((n + WG * vw - 1) / (WG * vw), VEC_MAX_WGS / vw); }
 
-// niter Arnoldi steps: nine launches each
+// One Arnoldi step from the product input p: nine launches.  With Z (the flexible method: p = M z is not a function of the basis alone) p is first kept
+// as column G_COUNT of Z, a tenth launch.
 template <int VW>
-int gmres_steps(const nh_csr *B, const unsigned char *rowmask, const double *dinv, double *V, double *z, double *w, double *work, int m, double stop_rr, int niter,
-                hipStream_t s) {
+int gmres_step(const nh_csr *B, const unsigned char *rowmask, const double *dinv, const double *p, double *Z, double *V, double *z, double *w, double *work, int m,
+               double stop_rr, hipStream_t s) {
   const i64 n = B->nrows;
   const dim3 grid(gs_grid(n, VW)), block(WG), sums((unsigned)std::min(m, 1024));
   Epilogue e;
   e.skip = work + G_ST;
-  for (int it = 0; it < niter; ++it) {
-    if (int rc = spmv(B, 1., z, 0., nullptr, rowmask, w, e, s)) return rc;
-    for (int second = 0; second < 2; ++second) {
-      hipLaunchKernelGGL((k_gmres_dots<GS_CHUNK, VW>), grid, block, 0, s, n, m, (const double *)V, (const double *)w, work);
-      NH_LAUNCH_CHECK();
-      hipLaunchKernelGGL(k_gmres_dots_sum, sums, block, 0, s, (int)grid.x, m, second, work);
-      NH_LAUNCH_CHECK();
-      if (second)
-        hipLaunchKernelGGL((k_gmres_axpy<GS_CHUNK, VW, true>), grid, block, 0, s, n, m, second, (const double *)V, w, work);
-      else
-        hipLaunchKernelGGL((k_gmres_axpy<GS_CHUNK, VW, false>), grid, block, 0, s, n, m, second, (const double *)V, w, work);
-      NH_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(k_gmres_scalars, dim3(1), block, 0, s, (int)grid.x, m, stop_rr, work);
-    NH_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_gmres_normalize<VW>, grid, block, 0, s, n, m, dinv, (const double *)w, V, z, (const double *)work);
+  if (Z) {
+    hipLaunchKernelGGL(k_gmres_keep<VW>, grid, block, 0, s, n, m, p, Z, (const double *)work);
     NH_LAUNCH_CHECK();
   }
+  if (int rc = spmv(B, 1., p, 0., nullptr, rowmask, w, e, s)) return rc;
+  for (int second = 0; second < 2; ++second) {
+    hipLaunchKernelGGL((k_gmres_dots<GS_CHUNK, VW>), grid, block, 0, s, n, m, (const double *)V, (const double *)w, work);
+    NH_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_gmres_dots_sum, sums, block, 0, s, (int)grid.x, m, second, work);
+    NH_LAUNCH_CHECK();
+    if (second)
+      hipLaunchKernelGGL((k_gmres_axpy<GS_CHUNK, VW, true>), grid, block, 0, s, n, m, second, (const double *)V, w, work);
+    else
+      hipLaunchKernelGGL((k_gmres_axpy<GS_CHUNK, VW, false>), grid, block, 0, s, n, m, second, (const double *)V, w, work);
+    NH_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_gmres_scalars, dim3(1), block, 0, s, (int)grid.x, m, stop_rr, work);
+  NH_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_gmres_normalize<VW>, grid, block, 0, s, n, m, dinv, (const double *)w, V, z, (const double *)work);
+  NH_LAUNCH_CHECK();
+  return NH_OK;
+}
+
+// niter Arnoldi steps with the fixed preconditioner: the product input of each is the z its predecessor left
+template <int VW>
+int gmres_steps(const nh_csr *B, const unsigned char *rowmask, const double *dinv, double *V, double *z, double *w, double *work, int m, double stop_rr, int niter,
+                hipStream_t s) {
+  for (int it = 0; it < niter; ++it)
+    if (int rc = gmres_step<VW>(B, rowmask, dinv, z, nullptr, V, z, w, work, m, stop_rr, s)) return rc;
   return NH_OK;
 }
 
@@ -1015,6 +1035,20 @@ int nh_csr_spmv_pq(const nh_csr *A, const double *p_dev, const unsigned char *ro
   Epilogue pq;
   pq.partial = partial_dev;
   return spmv(&B, 1., p_dev, 0., nullptr, rowmask_dev, q_dev, pq, s);
+}
+
+int nh_gmres_step_from(const nh_csr *A, const unsigned char *rowmask_dev, const double *t_dev, double *Z_dev, double *V_dev, double *z_dev, double *w_dev, double *work_dev,
+                       int restart, double stop_rr, hipStream_t s) {
+  if (int rc = check_csr("nh_gmres_step_from", A)) return rc;
+  NH_REQUIRE(A->nrows == A->ncols, "nh_gmres_step_from: the matrix must be square (got %lld x %lld)", (long long)A->nrows, (long long)A->ncols);
+  NH_REQUIRE(restart >= 1, "nh_gmres_step_from: restart must be at least 1 (got %d)", restart);
+  NH_REQUIRE(stop_rr >= 0., "nh_gmres_step_from: the bound on r . r must not be negative");
+  NH_REQUIRE(work_dev && (!A->nrows || (t_dev && Z_dev && V_dev && z_dev && w_dev)), "nh_gmres_step_from: NULL vector");
+  if (!A->nrows) return NH_OK;
+  nh_csr B = *A;
+  B.lanes = A->lanes ? A->lanes : nh_csr_lanes(A->nrows, A->nnz);
+  if (gs_pairs(A->nrows, {t_dev, Z_dev, V_dev, z_dev, w_dev})) return gmres_step<2>(&B, rowmask_dev, nullptr, t_dev, Z_dev, V_dev, z_dev, w_dev, work_dev, restart, stop_rr, s);
+  return gmres_step<1>(&B, rowmask_dev, nullptr, t_dev, Z_dev, V_dev, z_dev, w_dev, work_dev, restart, stop_rr, s);
 }
 
 extern "C" {

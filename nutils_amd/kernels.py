@@ -1241,3 +1241,11 @@ def pcg_iterate(values, rowptr, colidx, ncols, *, rowmask, amg, x, r, z, p, q, w
     moving once r . r is within the bound of `cg_stop`'''
     _lib.call('nh_pcg_iterate', ctypes.byref(_csr(values, rowptr, colidx, ncols, col32, lanes)), device.ptr(rowmask), amg._handle, device.ptr(x), device.ptr(r),
               device.ptr(z), device.ptr(p), device.ptr(q), device.ptr(work), int(niter), device.stream())
+
+
+def fgmres_iterate(values, rowptr, colidx, ncols, *, rowmask, amg, V, Z, z, t, w, work, restart, stop_rr, niter, col32=None, lanes=0):
+    '''enqueue `niter` steps of flexible GMRES preconditioned by the cycle of `amg` (nh_fgmres_iterate): t = M z, Z[count] = t, then the Arnoldi step of
+    `gmres_iterate` on A t; ten launches and a cycle each, nothing read back.  `V`: restart + 1 vectors, `Z`: restart; the cycle is started by
+    `gmres_init(None, ...)` and ended by `gmres_update(None, Z, ...)`.  A step past a stop moves nothing but still runs its cycle into `t`.'''
+    _lib.call('nh_fgmres_iterate', ctypes.byref(_csr(values, rowptr, colidx, ncols, col32, lanes)), device.ptr(rowmask), amg._handle, device.ptr(V), device.ptr(Z),
+              device.ptr(z), device.ptr(t), device.ptr(w), device.ptr(work), int(restart), float(stop_rr), int(niter), device.stream())

@@ -36,6 +36,11 @@ def solve(rec, atol, rtol, maxiter, check):
         rec.finish(flag)
 
 
+def _ready(precon):
+    from . import amg
+    return isinstance(precon, amg.Preconditioner)
+
+
 class Recurrence:
     '''What `solve` iterates.  `start()` puts the true residual mask(rhs - A x) into r, initialises the recurrence and returns r . r; `advance(steps, stop_rr)`
     enqueues `steps` iterations and returns (r . r, flag, count) from one small read-back, count the iterations since the start that count; `solution()` is x as
@@ -52,7 +57,10 @@ class Recurrence:
     def __init__(self, A, rhs, free, lhs, precon, on_device):
         from . import device, kernels
         self.A, self.kernels, self.csr = A, kernels, (*A.triplet(), A._ncols)
-        self.mask, self.x, self.b, self.dinv = A._krylov_setup(rhs, free, lhs, precon, on_device)
+        ready = precon if _ready(precon) else None  # (an object of `getprecon`, which `solve` has checked against the matrix and the mask)
+        self.mask, self.x, self.b, self.dinv = A._krylov_setup(rhs, free, lhs, None if ready else precon, on_device)
+        if ready and ready.kind == 'diag':
+            self.dinv = ready.dinv
         self.opts = dict(rowmask=self.mask, col32=A._columns(), lanes=A.lanes)
         self.vectors = lambda count, size=A.shape[0]: (device.empty(size, 'float64') for _ in range(count))
         (self.r,), x = self.vectors(1), self.x  # (no closure here or in a subclass holds `self`: a solve leaves no cycle behind to keep its vectors)
@@ -75,10 +83,11 @@ class Cg(Recurrence):
     count = 0
 
     def __init__(self, A, rhs, free, lhs, precon, on_device, preconargs):
-        super().__init__(A, rhs, free, lhs, None if precon == 'amg' else precon, on_device)
+        cycle = precon == 'amg' if isinstance(precon, str) else _ready(precon) and precon.kind == 'amg'
+        super().__init__(A, rhs, free, lhs, None if cycle else precon, on_device)
         k, csr, opts, dinv, x, r, (p, q) = self.kernels, self.csr, self.opts, self.dinv, self.x, self.r, self.vectors(2)
-        if precon == 'amg':  # z = M r is a V-cycle (nh_amg.hip); the rules are the same
-            hierarchy = A._amg_hierarchy(free, self.mask, *preconargs)
+        if cycle:  # z = M r is a V-cycle (nh_amg.hip); the rules are the same.  An object brings its hierarchy along: no numeric setup here
+            hierarchy = precon.hierarchy if _ready(precon) else A._amg_hierarchy(free, self.mask, *preconargs)
             (z,), work = self.vectors(1), k.pcg_work()
             self.init = lambda: k.pcg_init(hierarchy.handle, r, z, p, work)
             self.iterate = lambda steps: k.pcg_iterate(*csr, amg=hierarchy.handle, x=x, r=r, z=z, p=p, q=q, work=work, niter=steps, **opts)
@@ -128,20 +137,38 @@ class Minres(Recurrence):
 
 
 class Fgmres(Recurrence):
-    '''a start begins a cycle of up to `cycle` Arnoldi steps, which ends with x += M^-1 V y'''
+    '''a start begins a cycle of up to `cycle` Arnoldi steps, which ends with x += M^-1 V y.  With an 'amg' object the method is flexible in earnest: step j keeps
+    Z_j = M v_j, what the V-cycle returned, and the cycle ends with x += Z y: `cycle` more vectors on the device, 2 cycle + 1 in all.  A step enqueued past a
+    stop moves nothing but still runs its V-cycle, so a look of that variant enqueues no more steps than the cycle has left.'''
 
     name = 'fgmres'
     since = rr_start = None  # since: cycles finished since one ended on a vanished direction (0: the last one did)
+    left = None  # the 'amg' variant: the steps its cycle has left
 
     def __init__(self, A, rhs, free, lhs, precon, on_device, restart):
-        super().__init__(A, rhs, free, lhs, precon, on_device)
+        cycle = _ready(precon) and precon.kind == 'amg'
+        super().__init__(A, rhs, free, lhs, None if cycle else precon, on_device)
         m = self.cycle = max(1, min(restart, int(free.sum())))  # (a Krylov space has no more dimensions than there are free dofs)
         k, csr, opts, dinv, x, r, (z, w) = self.kernels, self.csr, self.opts, self.dinv, self.x, self.r, self.vectors(2)
         V, = self.vectors(1, (m + 1) * A.shape[0])
         work = self.work = k.gmres_work(m)
+        if cycle:
+            (t,), (Z,), hierarchy = self.vectors(1), self.vectors(1, m * A.shape[0]), precon.hierarchy  # (the closure keeps the hierarchy alive, as Cg's does)
+            self.left = m
+            self.init = lambda: k.gmres_init(None, r, V, z, work, restart=m)
+            self.iterate = lambda steps, stop_rr: k.fgmres_iterate(*csr, amg=hierarchy.handle, V=V, Z=Z, z=z, t=t, w=w, work=work, restart=m, stop_rr=stop_rr, niter=steps, **opts)
+            self.update = lambda: k.gmres_update(None, Z, x, work, restart=m)
+            return
         self.init = lambda: k.gmres_init(dinv, r, V, z, work, restart=m)
         self.iterate = lambda steps, stop_rr: k.gmres_iterate(*csr, dinv=dinv, V=V, z=z, w=w, work=work, restart=m, stop_rr=stop_rr, niter=steps, **opts)
         self.update = lambda: k.gmres_update(dinv, V, x, work, restart=m)
+
+    def advance(self, steps, stop_rr):
+        if self.left is None:
+            return super().advance(steps, stop_rr)
+        rr, flag, count = super().advance(min(steps, self.left), stop_rr)
+        self.left = self.cycle - int(count)
+        return rr, flag, count
 
     def admit(self, rr):
         if self.since in (0, 1) and not rr < self.rr_start:
@@ -156,3 +183,5 @@ class Fgmres(Recurrence):
     def finish(self, flag):
         self.since = 0 if flag else None if self.since is None else self.since + 1
         self.update()
+        if self.left is not None:
+            self.left = self.cycle  # (the next start begins a new cycle)

@@ -12,7 +12,9 @@ triplet in HBM as a ``HipMatrix``: products, the diagonal and four Jacobi-
 preconditioned Krylov solves -- conjugate gradients ('cg') for symmetric
 positive definite systems, MINRES ('minres') for symmetric indefinite ones,
 BiCGStab ('bicgstab') and restarted GMRES ('fgmres') for any square matrix --
-run on the device (nh_csr.hip); ``function.eval(function.as_matrix(K))`` builds
+run on the device (nh_csr.hip), 'cg' and 'fgmres' also with a multigrid
+cycle as preconditioner (``getprecon``: objects built once and used for
+several solves); ``function.eval(function.as_matrix(K))`` builds
 one without the triplet ever visiting the host, and so does ``solver.System``
 under this backend (``assemble_device``).  The matrix algebra runs there too
 (nh_csr_ops.hip): ``T``, ``submatrix`` by masks or strictly increasing indices,
@@ -542,6 +544,17 @@ class HipMatrix:
         bound without having fallen in that cycle (or in the
         one after it, which may get a direction of the size of a rounding and no further) the solve raises MatrixError('fgmres: singular matrix').
 
+        `precon` may also be an object that `getprecon` has built: `M = A.getprecon('amg', constrain=cons, symmetric=False)`, `A.solve(rhs, constrain=cons,
+        solver='fgmres', precon=M)`.  The object must have the shape of the matrix and the free mask of the solve (MatrixError otherwise, before any device work);
+        the values may differ: a preconditioner built on another matrix of the same pattern -- last step's Jacobian -- is the intended use, and a second solve
+        with it repeats no setup.  `preconargs` beside an object is a MatrixError.  A 'diag' object goes wherever precon='diag' goes, with the same bytes; an 'amg'
+        object goes to 'cg' if it was built with symmetric=True (the bytes of precon='amg') and to 'fgmres' always; 'bicgstab' and 'minres' refuse it.  With an
+        'amg' object 'fgmres' is flexible GMRES (nh_fgmres_iterate): step j keeps Z_j = M v_j, what the V-cycle returned, and the cycle ends with x += Z y, which
+        is right whatever the cycle is -- not symmetric, not convergent on its own, built from other values.  That is `restart` more vectors of n doubles on the
+        device, 2 restart + 1 in all; a step is ten launches and a V-cycle, and a look enqueues no more steps than the cycle has left, since a step past a stop
+        would still run its V-cycle.  Anything that is neither 'diag', 'amg', None nor such an object is an invalid preconditioner: Python callables are not
+        accepted, a host callback per step would undo the enqueued loop.
+
         solver='minres': MINRES of Paige and Saunders on the device for a SYMMETRIC matrix, definite or not, and ONE right-hand side, with the keywords, the row
         mask, the stopping rule and the true-residual restart of 'cg'.  One product and three launches an iteration, a three-term recurrence on a fixed handful
         of vectors.  `precon='diag'` is M^-1 = 1 / |A_ii| (MINRES needs a positive definite preconditioner; a zero on the diagonal of a free row is the
@@ -574,8 +587,18 @@ class HipMatrix:
             return x
         if not (atol > 0 or rtol > 0):
             raise MatrixError(f"solver {solver!r} needs a tolerance: pass atol or rtol (an iterative solve has no machine-precision mode)")
-        if precon == 'amg' and solver == 'cg':
-            from . import amg
+        from . import amg
+        ready = isinstance(precon, amg.Preconditioner)  # (built by `getprecon`: everything about it is checked here and below, before any device work)
+        if ready:
+            if preconargs is not None:
+                raise MatrixError('preconargs are the arguments of a preconditioner that `solve` builds; one that `getprecon` has built took them there')
+            if precon.shape != self.shape:
+                raise MatrixError(f'the preconditioner was built for a {precon.shape[0]}x{precon.shape[1]} matrix, this one is {nrows}x{ncols}')
+            if precon.kind == 'amg' and solver in ('bicgstab', 'minres'):
+                raise MatrixError(f"HipMatrix solver {solver!r} takes a 'diag' preconditioner or None; an 'amg' preconditioner goes to 'fgmres' (any matrix) or, built with symmetric=True, to 'cg'")
+            if solver == 'cg' and not precon.symmetric:
+                raise MatrixError("solver 'cg' needs a symmetric preconditioner, this one was built with symmetric=False: it goes to 'fgmres'")
+        elif precon == 'amg' and solver == 'cg':
             preconargs, setup = amg.split_setup(preconargs)
             preconargs, smoother = amg.split_smoother(preconargs)
             preconargs = amg.check_args(preconargs, ncols) + (smoother, setup)
@@ -586,6 +609,8 @@ class HipMatrix:
         if solver == 'fgmres' and not (isinstance(restart, (int, numpy.integer)) and not isinstance(restart, bool) and restart >= 1):
             raise MatrixError(f'fgmres: restart must be an integer of at least 1, got {restart!r}')
         free, lhs = constraints(ncols, _host(constrain), _host(lhs0))
+        if ready and not numpy.array_equal(precon.free, free):
+            raise MatrixError(f'the preconditioner was built for another set of free dofs ({int(precon.free.sum())} of them; this solve has {int(free.sum())}): build it with the constraints of the solve')
         from . import krylov
         maxiter, check = int(free.sum()) if maxiter is None else int(maxiter), max(1, int(check))
         args = self, rhs, free, lhs, precon, on_device
@@ -716,16 +741,56 @@ class HipMatrix:
         mask = None if free.all() else device.to_dev(free, 'uint8')
         x = device.to_dev(lhs, 'float64')
         b = device.zeros(n, 'float64') if rhs is None else rhs.contiguous() if on_device else device.to_dev(rhs, 'float64')
-        dinv = None
-        if precon == 'diag':
-            diag = self._diagonal_dev()
-            keep = diag.new_ones(n, dtype=bool) if mask is None else mask != 0
-            if bool(((diag == 0) & keep).any()):
-                raise MatrixError("building 'diag' preconditioner: diagonal has zero entries")
-            dinv = (1. / diag).masked_fill(~keep | (diag == 0), 0.)  # (constrained rows: any finite number, their residual is zero)
-        return mask, x, b, dinv
+        return mask, x, b, self._dinv(mask) if precon == 'diag' else None
 
-    def _amg_hierarchy(self, free, mask, coarse, sweeps, nullspace=None, smoother=None, setup=None):
+    def _dinv(self, mask):
+        '''the inverse diagonal on the rows the mask keeps, 0 elsewhere; a zero on a kept row is a MatrixError'''
+        diag = self._diagonal_dev()
+        keep = diag.new_ones(self.shape[0], dtype=bool) if mask is None else mask != 0
+        if bool(((diag == 0) & keep).any()):
+            raise MatrixError("building 'diag' preconditioner: diagonal has zero entries")
+        return (1. / diag).masked_fill(~keep | (diag == 0), 0.)  # (constrained rows: any finite number, their residual is zero)
+
+    def getprecon(self, precon, *, constrain=None, symmetric=True, **args):
+        '''A preconditioner object (Matrix.getprecon of the reference, matrix/_base.py): built once, applied by `M(r)` (numpy in, numpy out; device tensor in,
+        device tensor out) and taken by `solve(precon=M)` in place of a name, as often as wanted.  `constrain`: what `solve` takes (float with NaN on free dofs, or
+        bool); it fixes the row mask of the preconditioner, and a solve that uses it must select the same dofs.
+
+        'amg': the smoothed-aggregation V-cycle of `solve(solver='cg', precon='amg')`; `**args` are that solve's `preconargs` as keywords (coarse, sweeps,
+        nullspace, setup, smoother, degree, eigsteps, eigratio), checked by the same functions with the same messages.  The symbolic phase comes from and goes
+        to the matrix's cache as there, whatever `symmetric` is.  `symmetric=True` is exactly that hierarchy: `solve(solver='cg', precon=M)` returns the bytes of
+        the solve that builds its own, without the numeric setup.  `symmetric=False` is for a matrix that need not be symmetric (its pattern must be,
+        structurally: the aggregation says so otherwise): the dense level is inverted by the general pseudo-inverse, smoother='chebyshev' is a MatrixError (its
+        bound is a Lanczos estimate), everything else is the same; such an object goes to `solve(solver='fgmres')` alone.
+        'diag': the inverse diagonal, for every solver that takes precon='diag', with the same bytes on the same matrix; no arguments.
+
+        The object keeps alive what it reads: the hierarchy with its handle and level values, the value tensor it was built on, the masks.  It may be used on
+        another matrix of the same shape and pattern (a matrix made by `_with_values`: the next Newton step, K + c M): that is a lagged preconditioner, which
+        flexible GMRES tolerates by construction and CG as long as the object stays symmetric positive definite.  Argument errors are a MatrixError before any
+        device work.'''
+        from . import amg, device
+        nrows, ncols = self.shape
+        if nrows != ncols:
+            raise MatrixError(f'constrained matrix is not square: {nrows}x{ncols}')
+        if precon == 'amg':
+            rest, setup = amg.split_setup(args)
+            rest, smoother = amg.split_smoother(rest)
+            if smoother is not None and not symmetric:
+                raise MatrixError("amg: smoother='chebyshev' takes its bound from a Lanczos estimate, which needs a symmetric matrix; with symmetric=False the smoother is 'jacobi'")
+            coarse, sweeps, nullspace = amg.check_args(rest, ncols)
+        elif precon == 'diag':
+            if args:
+                raise MatrixError(f"invalid arguments {sorted(args)} for the 'diag' preconditioner: it takes none")
+        else:
+            raise MatrixError(f"invalid preconditioner {precon!r} for HipMatrix.getprecon: 'diag' or 'amg'")
+        free, _ = constraints(ncols, _host(constrain))
+        mask = None if free.all() else device.to_dev(free, 'uint8')
+        if precon == 'diag':
+            return amg.Preconditioner('diag', self.shape, free, True, self.triplet()[0], mask, dinv=self._dinv(mask))
+        hierarchy = self._amg_hierarchy(free, mask, coarse, sweeps, nullspace, smoother, setup, symmetric=bool(symmetric))
+        return amg.Preconditioner('amg', self.shape, free, symmetric, self.triplet()[0], mask, hierarchy=hierarchy)
+
+    def _amg_hierarchy(self, free, mask, coarse, sweeps, nullspace=None, smoother=None, setup=None, *, symmetric=True):
         '''the hierarchy of an 'amg' preconditioner (amg.Hierarchy): the symbolic phase is taken from the cache if it was made for this mask, this `coarse`,
         this number of near-nullspace vectors and this `setup`, the numeric phase runs on the values of this matrix (the smoother belongs to it: the cache
         does not know it)'''
@@ -736,7 +801,7 @@ class HipMatrix:
             self._amg = free.copy(), coarse, k, amg.symbolic(rowptr, colidx, None if mask is None else mask != 0, coarse, k, setup=setup), setup
         if nullspace is not None:  # PCIe: a host array goes up once, n k doubles
             nullspace = nullspace.contiguous() if _is_tensor(nullspace) else device.to_dev(nullspace, 'float64')
-        return amg.Hierarchy(self._amg[3], self.triplet()[0], sweeps, nullspace, smoother)
+        return amg.Hierarchy(self._amg[3], self.triplet()[0], sweeps, nullspace, smoother, symmetric)
 
 
 class _HipBackend:

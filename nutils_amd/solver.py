@@ -438,7 +438,8 @@ class System:
         rtol = 1e-3 unless `linargs` names a tolerance.  Under a matrix backend that takes device tensors (`matrix.backend('hip')`) the Jacobian stays in HBM
         and the constraints are the row mask of its solve; that solve is iterative, so `linargs` must name a `solver` ('cg' for symmetric positive definite
         systems, 'minres' for symmetric indefinite ones, 'bicgstab' or 'fgmres' for any square one) and a tolerance; `linear_iterations` then lists the iterations (for 'fgmres': Arnoldi steps) of every
-        linear solve.'''
+        linear solve.  The objects of `linargs` reach `solve` as they are, so a preconditioner built once on the Jacobian of an earlier step
+        (`HipMatrix.getprecon`) may be handed on: `linargs=dict(solver='fgmres', precon=M, rtol=1e-10)`.'''
         x, free = self._pack(dict(arguments or {}), constrain)
         args = self._unpack(dict(arguments or {}), x)
         if not self.is_linear and tol <= 0:

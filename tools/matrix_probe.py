@@ -38,10 +38,15 @@
     `spmv` in the same process, their windows alternating, with the algorithmic bytes of each -- nnz (8 + 4) + nrows 8 + k (nrows + ncols) 8 for the block product,
     which reads every (value, column) pair once, k (nnz (8 + 4) + nrows 16 + ncols 8) for the k products -- and the time of a batched CG iteration against k
     single-vector iterations (each timed call restores the residuals, starts the recurrences and enqueues 20 iterations, so that no window runs into convergence;
-    the time is that call over 20).
+    the time is that call over 20),
+  * for flexible GMRES with the AMG cycle (section 'flexible', not in the default; nh_fgmres_iterate): on the nonsymmetric twin, the setup of a preconditioner
+    object (`getprecon('amg', symmetric=False)`, with and without the symbolic phase: the second is what a reused object saves every later solve), at restart
+    10 and 30 the time of a step against a Jacobi-GMRES step and one cycle of the same run, their windows alternating, and steps, wall time (the median of
+    three) and true residual of the solve to rtol = 1e-8 against Jacobi-GMRES at the same restart and Jacobi-BiCGStab in the same process; and a solve of
+    the matrix one perturbation of the values further (off-diagonal entries scaled by factors within 10 % of one) with the old object against its own.
 
 Usage: python tools/matrix_probe.py [--matrices poisson128,elasticity96,elasticity64,elasticity48,bilinear2048,bilinear1024,p2vector32,p2vector16] [--scale 1.0]
-[--sections spmv,cg,bicgstab,fgmres,minres,amg,smoother,algebra,columns] [--amg-setup entry,block] [--eigratios 4,10,30] [--eigsteps 5,10,20] [--out FILE]
+[--sections spmv,cg,bicgstab,fgmres,minres,amg,smoother,algebra,columns,flexible] [--amg-setup entry,block] [--eigratios 4,10,30] [--eigsteps 5,10,20] [--out FILE]
 (--scale shrinks every mesh for a quick look; --sections leaves parts out).  Not run by any test.'''
 import argparse
 import json
@@ -179,6 +184,8 @@ def probe(name, args):
         info['algebra'] = probe_algebra(A, free, args)
     if 'columns' in args.sections:
         info['columns'] = probe_columns(A, free, mask, args)
+    if 'flexible' in args.sections:
+        info['flexible'] = probe_flexible(A, free, mask, rhs_dev, res0, info, args)
     return info
 
 
@@ -622,6 +629,104 @@ def probe_bicgstab(A, free, mask, rhs_dev, res0, args):
         y, code = scipy.sparse.linalg.bicgstab(F, b, tol=1e-8, atol=0., maxiter=args.maxiter, M=jacobi, callback=lambda _: count.__setitem__(0, count[0] + 1))
     out['host'].update(bicgstab_ms=(time.perf_counter() - t0) * 1e3, iterations=count[0], converged=code == 0,
                        true_relative_residual=float(numpy.linalg.norm(b - F @ y) / numpy.linalg.norm(b)))
+    return out
+
+
+FLEX_RESTARTS = (10, 30)
+
+
+def probe_flexible(A, free, mask, rhs_dev, res0, info, args):
+    '''the nonsymmetric twin of A under flexible GMRES with the AMG cycle as its preconditioner (an object of `getprecon`, symmetric=False; the rigid-body modes
+    for a vector matrix): setup, the time of a step against a Jacobi-GMRES step and a cycle of the same run, and the solve against Jacobi-GMRES and
+    Jacobi-BiCGStab in the same process, alternating; what a reused object saves; a solve with the object of the matrix before a perturbation of the values'''
+    import torch
+    from nutils_amd import amg, device, kernels, matrix
+    _, rowptr, colidx = A.triplet()
+    nrows, ncols = A.shape
+    N = nonsymmetric_twin(A)
+    nvalues = N.triplet()[0]
+    out = {}
+
+    def clocked(fn):
+        device.synchronize()
+        t0 = time.perf_counter()
+        result = fn()
+        device.synchronize()
+        return result, (time.perf_counter() - t0) * 1e3
+
+    pargs = dict(constrain=~free, symmetric=False)
+    if info['components'] > 1:
+        pargs['nullspace'] = device.to_dev(amg.rigid_body_modes(nodes_of(info)), 'float64')
+    try:
+        M, out['getprecon_first_ms'] = clocked(lambda: N.getprecon('amg', **pargs))  # (with the symbolic phase)
+        M, out['getprecon_ms'] = clocked(lambda: N.getprecon('amg', **pargs))  # (the numeric setup: what a reused object saves a solve)
+    except (matrix.MatrixError, RuntimeError) as e:  # (a plan beyond its int32 indices, or out of memory: recorded, not hidden)
+        return dict(error=f'{type(e).__name__}: {e}')
+    out['levels'] = [lv.nfree for lv in M.hierarchy.levels]
+    dinv = (1. / N._diagonal_dev()).masked_fill(mask == 0, 0.)
+    r0 = torch.from_numpy(numpy.random.default_rng(1).normal(size=nrows) * free).cuda()
+    z, t, w = torch.zeros_like(r0), torch.zeros_like(r0), torch.zeros_like(r0)
+    csr = dict(rowmask=mask, col32=A._columns(), lanes=A.lanes)
+
+    def timed_solve(**kwargs):
+        def run():
+            try:
+                return N.solve(rhs_dev, constrain=~free, rtol=1e-8, maxiter=args.maxiter, **kwargs), True
+            except matrix.ToleranceNotReached as e:
+                return e.best, False
+        runs = [clocked(run) for _ in range(3)]
+        (sol, converged), _ = runs[0]
+        times = [ms for _, ms in runs]
+        return dict(converged=converged, wall_ms=float(numpy.median(times)), spread=(max(times) - min(times)) / float(numpy.median(times)), iterations=N.iterations,
+                    true_relative_residual=float(N.spmv(sol, alpha=-1., beta=1., b=rhs_dev, rowmask=mask).norm() / res0.norm()))
+
+    for m in FLEX_RESTARTS:
+        V, Z = (torch.zeros(k * nrows, dtype=torch.float64, device='cuda') for k in (m + 1, m))
+        work = kernels.gmres_work(m)
+        start_j, start_f = (lambda: kernels.gmres_init(dinv, r0, V, z, work, restart=m)), (lambda: kernels.gmres_init(None, r0, V, z, work, restart=m))
+
+        def jacobi():  # a whole cycle from the same residual, none of its steps stopped (the bound is zero)
+            start_j()
+            kernels.gmres_iterate(nvalues, rowptr, colidx, ncols, dinv=dinv, V=V, z=z, w=w, work=work, restart=m, stop_rr=0., niter=m, **csr)
+
+        def flexible():
+            start_f()
+            kernels.fgmres_iterate(nvalues, rowptr, colidx, ncols, amg=M.hierarchy.handle, V=V, Z=Z, z=z, t=t, w=w, work=work, restart=m, stop_rr=0., niter=m, **csr)
+
+        t_flex, t_jac, t_sf, t_sj, t_cycle = windows([flexible, jacobi, start_f, start_j, lambda: M.hierarchy.apply(z, t)], args.window)
+        flexible()
+        res = dict(steps_per_call=work[:3].tolist()[2], basis_vectors=2 * m + 1, basis_bytes=(2 * m + 1) * 8 * nrows)
+        res['step'] = stats([(a - b) / m for a, b in zip(t_flex, t_sf)])
+        res['jacobi_step'] = stats([(a - b) / m for a, b in zip(t_jac, t_sj)])
+        res['cycle'] = stats(t_cycle)
+        res['cycle_share'] = res['cycle']['us'] / res['step']['us']
+        res['step_over_jacobi_step'] = res['step']['us'] / res['jacobi_step']['us']
+        del V, Z, work
+        res['solve'] = timed_solve(solver='fgmres', precon=M, restart=m)
+        res['solve_jacobi'] = timed_solve(solver='fgmres', precon='diag', restart=m)
+        res['solve_over_jacobi'] = res['solve']['wall_ms'] / res['solve_jacobi']['wall_ms']
+        torch.cuda.empty_cache()
+        out[str(m)] = res
+    out['solve_bicgstab'] = timed_solve(solver='bicgstab', precon='diag')
+    # lagged: the object of N on the matrix one perturbation of the values further (every entry scaled by a factor within 10 % of one; the diagonal kept, so
+    # the matrix stays as dominant as it was), against that matrix's own object
+    scale = 1 + .1 * torch.from_numpy(numpy.random.default_rng(3).uniform(-1, 1, nvalues.numel())).cuda()
+    rows = torch.repeat_interleave(torch.arange(nrows, device=nvalues.device), rowptr[1:] - rowptr[:-1])
+    N2 = N._with_values(torch.where(rows == colidx, nvalues, nvalues * scale))
+
+    def lagged(precon):
+        device.synchronize()
+        t0 = time.perf_counter()
+        try:
+            sol, converged = N2.solve(rhs_dev, constrain=~free, solver='fgmres', precon=precon, restart=30, rtol=1e-8, maxiter=args.maxiter), True
+        except matrix.ToleranceNotReached as e:
+            sol, converged = e.best, False
+        device.synchronize()
+        return dict(converged=converged, wall_ms=(time.perf_counter() - t0) * 1e3, iterations=N2.iterations,
+                    true_relative_residual=float(N2.spmv(sol, alpha=-1., beta=1., b=rhs_dev, rowmask=mask).norm() / res0.norm()))
+
+    own, out['lagged_own_setup_ms'] = clocked(lambda: N2.getprecon('amg', **pargs))
+    out['lagged'] = dict(own=lagged(own), lagged=lagged(M))
     return out
 
 
