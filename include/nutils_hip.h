@@ -941,6 +941,30 @@ int nh_pcg_iterate(const nh_csr *A, const unsigned char *rowmask_dev, const nh_a
 int nh_fgmres_iterate(const nh_csr *A, const unsigned char *rowmask_dev, const nh_amg *amg, double *V_dev, double *Z_dev, double *z_dev, double *t_dev, double *w_dev,
                       double *work_dev, int restart, double stop_rr, int niter, void *stream);
 
+/* ---- a block preconditioner for saddle-point systems K = [[A, Bt], [B, C]] (nh_amg.hip) ----------------------
+ * The dofs are split into a first field (mask1) and a second; M is the block upper-triangular solve with the AMG cycle on the first block and a diagonal
+ * approximation shat of the Schur complement on the second: z2 = sinv r, t = mask1(r - K z2), z1 = cycle(t), z = z1 + z2, all on vectors of n doubles.
+ * nh_csr_schur_diagonal: out[i] = A_ii - sum over the entries k of row i with first[col[k]] != 0 of values[k] vt[k] dinv[col[k]], for every row of a square A;
+ * vt_dev: the values of A^T on A's pattern (which must then be structurally symmetric: the caller's to see to), first_dev uint8 [n], dinv_dev double [n].  With
+ * first the mask of the first field and dinv = 1 / diag there this is the SIMPLE diagonal of C - B diag(A)^-1 Bt on the rows of the second field.  The mapping
+ * of nh_csr_spmv (A->lanes lanes per row, int32 or int64 columns), both sums folded in its order, nothing atomic: repeated calls are bit-identical.  A matrix
+ * without entries is zero-filled without a launch.
+ * nh_schur is a handle that holds views and owns no device memory: the hierarchy of the first block (built on K with the mask of the first field as its row
+ * mask; it must outlive the handle), the view of K, mask1_dev uint8 [n], sinv_dev double [n] (1 / shat on the second field's free dofs, 0 elsewhere) and two
+ * scratch vectors of n doubles, distinct.  nh_schur_apply enqueues z = M r: z2 = sinv r where sinv != 0 and +0 elsewhere (r is not read off the second field
+ * there, nor on rows outside mask1 by the product), the masked product nh_csr_spmv(K, -1, z2, 1, r, mask1, t), the cycle of nh_amg_apply from t into z, and
+ * z += z2: two launches, a product and a cycle.  r_dev and z_dev: n doubles, distinct, and neither a scratch vector of the handle.
+ * nh_fgmres_iterate_schur is nh_fgmres_iterate with that application in place of the cycle: the same vectors, work array, rules and Arnoldi step; A is the
+ * matrix of the solve, which may have other values than the K of the handle (a lagged preconditioner).  A NULL handle, matrix or vector, sizes that differ,
+ * restart < 1, a negative niter or stop_rr and a matrix that is not square are NH_EINVAL before a launch. */
+typedef struct nh_schur nh_schur;
+int nh_csr_schur_diagonal(const nh_csr *A, const double *vt_dev, const unsigned char *first_dev, const double *dinv_dev, double *out_dev, void *stream);
+int nh_schur_create(const nh_amg *first, const nh_csr *K, const unsigned char *mask1_dev, const double *sinv_dev, double *z2_dev, double *t_dev, nh_schur **out);
+int nh_schur_free(nh_schur *schur);
+int nh_schur_apply(const nh_schur *schur, const double *r_dev, double *z_dev, void *stream);
+int nh_fgmres_iterate_schur(const nh_csr *A, const unsigned char *rowmask_dev, const nh_schur *schur, double *V_dev, double *Z_dev, double *z_dev, double *t_dev,
+                            double *w_dev, double *work_dev, int restart, double stop_rr, int niter, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

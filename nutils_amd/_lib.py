@@ -245,6 +245,11 @@ SIGNATURES = {
     'nh_pcg_init': (ctypes.c_int, [c_i64, vp, vp, vp, vp, vp, vp]),
     'nh_pcg_iterate': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int, vp]),
     'nh_fgmres_iterate': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, vp]),
+    'nh_csr_schur_diagonal': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, vp, vp, vp]),
+    'nh_schur_create': (ctypes.c_int, [vp, ctypes.POINTER(Csr), vp, vp, vp, vp, ctypes.POINTER(vp)]),
+    'nh_schur_free': (ctypes.c_int, [vp]),
+    'nh_schur_apply': (ctypes.c_int, [vp, vp, vp, vp]),
+    'nh_fgmres_iterate_schur': (ctypes.c_int, [ctypes.POINTER(Csr), vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int, ctypes.c_double, ctypes.c_int, vp]),
 }
 
 _lib = None

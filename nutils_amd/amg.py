@@ -1,5 +1,5 @@
 '''Smoothed-aggregation algebraic multigrid for ``HipMatrix.solve(solver='cg', precon='amg')`` and, as an object of ``HipMatrix.getprecon`` (``Preconditioner``),
-for ``solve(solver='cg' | 'fgmres', precon=M)``.
+for ``solve(solver='cg' | 'fgmres', precon=M)``; on a masked first block it is also half of the block preconditioner of a saddle point (``Schur``).
 
 Two phases.  ``symbolic`` reads the pattern and the constraint mask only and is written with torch tensor operations that run wherever their inputs
 live (on the device in a solve, on CPU tensors in the tests): the aggregates, the CSR patterns of the prolongator P, the restriction R = P^T and the
@@ -674,23 +674,40 @@ class Hierarchy:
         return self.handle.apply(r, z)
 
 
+class Schur:
+    '''The block upper-triangular preconditioner of a saddle point K = [[A, Bt], [B, C]] on the device (``HipMatrix.getprecon('schur')``; nh_schur_*): `first`, the
+    ``Hierarchy`` built on K itself with the first field's free dofs `mask1` as its row mask (no submatrix is formed), and `sinv`, 1 / shat on the second field's
+    free dofs and 0 elsewhere, shat the diagonal approximation of the Schur complement.  z = M r is z2 = sinv r, t = mask1(r - K z2), z1 = cycle(t), z = z1 + z2 on
+    full-length vectors; r is not read on held dofs and z is zero there.  `csr`: the matrix as (values, rowptr, colidx, ncols, col32, lanes).'''
+
+    def __init__(self, first, csr, mask1, sinv):
+        from . import kernels
+        self.first, self.mask1, self.sinv = first, mask1, sinv
+        self.handle = kernels.Schur(first.handle, csr, mask1, sinv)
+
+    def apply(self, r, z=None):
+        '''z = M r, one application (nh_schur_apply)'''
+        return self.handle.apply(r, z)
+
+
 class Preconditioner:
     '''What ``HipMatrix.getprecon`` returns (the reference's Matrix.getprecon, matrix/_base.py): a preconditioner built once, applied by `M(r)` and taken by
     ``HipMatrix.solve(precon=M)`` in place of a name, on the matrix it was built on or on any other of the same shape, pattern and free mask -- the next Newton
-    step's, say.  `kind`: 'amg' (`hierarchy`: the ``Hierarchy``, whose handle, level values and scratch vectors live as long as this object) or 'diag' (`dinv`:
-    the inverse diagonal, 0 on constrained rows); `shape`: of the matrix; `free`: the host bool mask of the free dofs it was built for; `mask`: the same on the
-    device (None: all free); `values`: the value tensor it was built on; `symmetric`: whether the operator may precondition conjugate gradients.'''
+    step's, say.  `kind`: 'amg' (`hierarchy`: the ``Hierarchy``, whose handle, level values and scratch vectors live as long as this object), 'diag' (`dinv`:
+    the inverse diagonal, 0 on constrained rows) or 'schur' (`schur`: the ``Schur`` operator of a saddle point, whose first block's hierarchy is also `hierarchy`);
+    `shape`: of the matrix; `free`: the host bool mask of the free dofs it was built for; `mask`: the same on
+    the device (None: all free); `values`: the value tensor it was built on; `symmetric`: whether the operator may precondition conjugate gradients.'''
 
-    def __init__(self, kind, shape, free, symmetric, values, mask, *, hierarchy=None, dinv=None):
+    def __init__(self, kind, shape, free, symmetric, values, mask, *, hierarchy=None, dinv=None, schur=None):
         self.kind, self.shape, self.free, self.symmetric, self.values, self.mask = kind, tuple(shape), free, bool(symmetric), values, mask
-        self.hierarchy, self.dinv = hierarchy, dinv
+        self.hierarchy, self.dinv, self.schur = hierarchy, dinv, schur
 
     def __repr__(self):
         return f'<{self.kind!r} preconditioner of a {self.shape[0]}x{self.shape[1]} HipMatrix, {int(self.free.sum())} free dofs, symmetric={self.symmetric}>'
 
     def __call__(self, r):
         '''z = M r, one application: a numpy vector gives a numpy vector, a float64 device tensor a device tensor.  'amg': one V-cycle (``Hierarchy.apply``) on r
-        as it is given; 'diag': dinv r.'''
+        as it is given; 'diag': dinv r; 'schur': the block solve (``Schur.apply``).'''
         from . import device
         tensor = type(r).__module__.split('.')[0] == 'torch'
         if not tensor:
@@ -698,5 +715,5 @@ class Preconditioner:
         if r.ndim != 1 or r.shape[0] != self.shape[0] or (tensor and str(r.dtype) != 'torch.float64'):
             raise _error()(f'a preconditioner of a {self.shape[0]}x{self.shape[1]} matrix takes a float64 vector of {self.shape[0]} entries, got {tuple(r.shape)} {r.dtype}')
         rdev = r.contiguous() if tensor else device.to_dev(r, 'float64')
-        z = self.hierarchy.apply(rdev) if self.kind == 'amg' else self.dinv * rdev
+        z = self.hierarchy.apply(rdev) if self.kind == 'amg' else self.schur.apply(rdev) if self.kind == 'schur' else self.dinv * rdev
         return z if tensor else device.to_host(z)

@@ -24,6 +24,9 @@
 //     prolongate-and-add); with one sweep that is five launches per level and one for the coarsest.
 //   * nh_fgmres_iterate: flexible GMRES with the cycle as its preconditioner: t = M z by amg_cycle, then the Arnoldi step of nh_csr.hip from the product input t
 //     (nh_gmres_step_from), which keeps t as a column of Z.  No kernel of its own here.
+//   * the block preconditioner of a saddle point K = [[A, Bt], [B, C]] (nh_schur_*): k_schur_diagonal<L, Idx> forms the SIMPLE diagonal of the approximate Schur
+//     complement on the mapping of k_csr_spmv; the application z2 = sinv r (k_schur_scale), t = mask1(r - K z2) (nh_csr_spmv), z1 = cycle(t) (amg_cycle on the
+//     hierarchy of the first block), z = z1 + z2 (k_schur_merge) is a host sequence; nh_fgmres_iterate_schur is nh_fgmres_iterate with that application.
 //   * k_pcg_*: CG with z = M r handed in.  An iteration: q = mask(A p) with the partials of p . q (the DOT = 1 product of nh_csr.hip); update (alpha, x,
 //     r, partials of r . r); the cycle; partials of r . z; direction (beta, p = z + beta p).  The cell discipline is that of k_cg_update / k_cg_direction.
 #include "nh_common.h"
@@ -35,6 +38,16 @@
 
 struct nh_amg {
   std::vector<nh_amg_level> levels;
+};
+
+// views, like nh_amg: the hierarchy of the first block, the matrix the operator was built on, the mask of the first field, the inverse Schur diagonal (0 off the
+// second field) and two scratch vectors
+struct nh_schur {
+  const nh_amg *first;
+  nh_csr K;
+  const unsigned char *mask1;
+  const double *sinv;
+  double *z2, *t;
 };
 
 namespace {
@@ -214,6 +227,49 @@ __global__ __launch_bounds__(WG) void k_jacobi(i64 nrows, const i64 *__restrict_
 
 __global__ __launch_bounds__(WG) void k_scale(i64 n, const double *__restrict__ w, const double *__restrict__ b, double *__restrict__ y) {
   for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < n; i += (i64)gridDim.x * WG) y[i] = w[i] * b[i];
+}
+
+// out[row] = A[row, row] - sum over the entries k of the row with first[col[k]] of values[k] vt[k] dinv[col[k]]: the diagonal of C - B diag(A)^-1 Bt on the rows of
+// the second field when vt holds the values of the transpose on the same pattern, first marks the first field and dinv = 1 / diag there.  The mapping and the
+// fold of k_csr_spmv, for the two sums.
+template <int L, class Idx>
+__global__ __launch_bounds__(WG) void k_schur_diagonal(i64 nrows, const i64 *__restrict__ rowptr, const Idx *__restrict__ col, const double *__restrict__ values,
+                                                       const double *__restrict__ vt, const unsigned char *__restrict__ first, const double *__restrict__ dinv,
+                                                       double *__restrict__ out) {
+  constexpr int G = WG / L;
+  const int lane = threadIdx.x & (L - 1);
+  for (i64 base = (i64)blockIdx.x * G; base < nrows; base += (i64)gridDim.x * G) {  // (uniform trip count: every lane takes part in the shuffles)
+    const i64 row = base + threadIdx.x / L;
+    const bool live = row < nrows;
+    double d = 0, s = 0;
+    if (live) {
+      const i64 k1 = rowptr[row + 1];
+      for (i64 k = rowptr[row] + lane; k < k1; k += L) {
+        const i64 c = (i64)col[k];
+        if (c == row) d += values[k];
+        if (first[c]) s += values[k] * vt[k] * dinv[c];
+      }
+    }
+#pragma unroll
+    for (int o = L >> 1; o; o >>= 1) {
+      d += __shfl_xor(d, o, L);
+      s += __shfl_xor(s, o, L);
+    }
+    if (live && lane == 0) out[row] = d - s;
+  }
+}
+
+// z2 = sinv r where sinv != 0 (the second field), +0 elsewhere: r is not read off the second field
+__global__ __launch_bounds__(WG) void k_schur_scale(i64 n, const double *__restrict__ sinv, const double *__restrict__ r, double *__restrict__ z2) {
+  for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < n; i += (i64)gridDim.x * WG) {
+    const double w = sinv[i];
+    z2[i] = w != 0. ? w * r[i] : 0.;
+  }
+}
+
+// z += z2: the two parts have disjoint supports
+__global__ __launch_bounds__(WG) void k_schur_merge(i64 n, const double *__restrict__ z2, double *__restrict__ z) {
+  for (i64 i = (i64)blockIdx.x * WG + threadIdx.x; i < n; i += (i64)gridDim.x * WG) z[i] += z2[i];
 }
 
 // One step of the Chebyshev smoother: dout = c1 d + c2 dinv (b - A x), y = x + dout on the rows the mask keeps, +0 in both elsewhere (k_jacobi with another
@@ -625,6 +681,40 @@ int amg_cycle(const nh_amg *h, size_t l, const double *b, double *x, hipStream_t
   return NH_OK;  // (cur == x)
 }
 
+template <class Idx>
+void launch_schur_diagonal(int L, const nh_csr &A, const Idx *col, const double *vt, const unsigned char *first, const double *dinv, double *out, hipStream_t s) {
+#define NH_SCHURDIAG(LL)                                                                                                                                          \
+  case LL:                                                                                                                                                        \
+    hipLaunchKernelGGL((k_schur_diagonal<LL, Idx>), dim3(spmv_grid(A.nrows, LL)), dim3(WG), 0, s, (i64)A.nrows, (const i64 *)A.rowptr_dev, col, A.values_dev, vt, \
+                       first, dinv, out);                                                                                                                         \
+    break;
+  switch (L) {
+    NH_SCHURDIAG(1)
+    NH_SCHURDIAG(2)
+    NH_SCHURDIAG(4)
+    NH_SCHURDIAG(8)
+    NH_SCHURDIAG(16)
+    NH_SCHURDIAG(32)
+    default:
+    NH_SCHURDIAG(64)
+  }
+#undef NH_SCHURDIAG
+}
+
+// z = M r, the block upper-triangular solve: four steps on full-length vectors, the cycle in between
+int schur_apply(const nh_schur *h, const double *r, double *z, hipStream_t s) {
+  const i64 n = h->K.nrows;
+  if (!n) return NH_OK;
+  const unsigned grid = vec_grid(n);
+  hipLaunchKernelGGL(k_schur_scale, dim3(grid), dim3(WG), 0, s, n, h->sinv, r, h->z2);
+  NH_LAUNCH_CHECK();
+  if (int rc = nh_csr_spmv(&h->K, -1., h->z2, 1., r, h->mask1, h->t, s)) return rc;
+  if (int rc = amg_cycle(h->first, 0, h->t, z, s)) return rc;
+  hipLaunchKernelGGL(k_schur_merge, dim3(grid), dim3(WG), 0, s, n, (const double *)h->z2, z);
+  NH_LAUNCH_CHECK();
+  return NH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -895,6 +985,73 @@ int nh_fgmres_iterate(const nh_csr *A, const unsigned char *rowmask_dev, const n
   hipStream_t s = nh_stream(stream);
   for (int it = 0; it < niter; ++it) {
     if (int rc = amg_cycle(amg, 0, z_dev, t_dev, s)) return rc;  // (also past a stop: the cycle reads no status, its result then goes nowhere)
+    if (int rc = nh_gmres_step_from(A, rowmask_dev, t_dev, Z_dev, V_dev, z_dev, w_dev, work_dev, restart, stop_rr, s)) return rc;
+  }
+  return NH_OK;
+}
+
+int nh_csr_schur_diagonal(const nh_csr *A, const double *vt_dev, const unsigned char *first_dev, const double *dinv_dev, double *out_dev, void *stream) {
+  if (int rc = check_csr("nh_csr_schur_diagonal", A)) return rc;
+  NH_REQUIRE(A->nrows == A->ncols, "nh_csr_schur_diagonal: the matrix must be square (got %lld x %lld)", (long long)A->nrows, (long long)A->ncols);
+  NH_REQUIRE(!A->nrows || out_dev, "nh_csr_schur_diagonal: NULL result vector");
+  NH_REQUIRE(!A->nnz || (vt_dev && first_dev && dinv_dev), "nh_csr_schur_diagonal: NULL transposed values, field mask or inverse diagonal");
+  if (!A->nrows) return NH_OK;
+  hipStream_t s = nh_stream(stream);
+  if (!A->nnz) {
+    NH_CHECK_HIP(hipMemsetAsync(out_dev, 0, sizeof(double) * (size_t)A->nrows, s));
+    return NH_OK;
+  }
+  const int L = A->lanes ? A->lanes : nh_csr_lanes(A->nrows, A->nnz);
+  if (A->col32_dev)
+    launch_schur_diagonal(L, *A, A->col32_dev, vt_dev, first_dev, dinv_dev, out_dev, s);
+  else
+    launch_schur_diagonal(L, *A, (const i64 *)A->colidx_dev, vt_dev, first_dev, dinv_dev, out_dev, s);
+  NH_LAUNCH_CHECK();
+  return NH_OK;
+}
+
+int nh_schur_create(const nh_amg *first, const nh_csr *K, const unsigned char *mask1_dev, const double *sinv_dev, double *z2_dev, double *t_dev, nh_schur **out) {
+  NH_REQUIRE(out, "nh_schur_create: nowhere to put the handle");
+  NH_REQUIRE(first, "nh_schur_create: NULL hierarchy of the first block");
+  if (int rc = check_csr("nh_schur_create", K)) return rc;
+  NH_REQUIRE(K->nrows == K->ncols, "nh_schur_create: the matrix must be square (got %lld x %lld)", (long long)K->nrows, (long long)K->ncols);
+  NH_REQUIRE(first->levels[0].A.nrows == K->nrows, "nh_schur_create: a hierarchy of another size (%lld rows, the matrix has %lld)", (long long)first->levels[0].A.nrows,
+             (long long)K->nrows);
+  NH_REQUIRE(!K->nrows || (mask1_dev && sinv_dev && z2_dev && t_dev), "nh_schur_create: NULL mask, Schur diagonal or scratch vector");
+  NH_REQUIRE(!K->nrows || z2_dev != t_dev, "nh_schur_create: the two scratch vectors must be distinct");
+  nh_schur *h = new (std::nothrow) nh_schur{first, *K, mask1_dev, sinv_dev, z2_dev, t_dev};
+  NH_REQUIRE(h, "nh_schur_create: out of memory");
+  *out = h;
+  return NH_OK;
+}
+
+int nh_schur_free(nh_schur *schur) {
+  delete schur;
+  return NH_OK;
+}
+
+int nh_schur_apply(const nh_schur *schur, const double *r_dev, double *z_dev, void *stream) {
+  NH_REQUIRE(schur, "nh_schur_apply: NULL preconditioner");
+  NH_REQUIRE(!schur->K.nrows || (r_dev && z_dev && r_dev != z_dev), "nh_schur_apply: NULL vector, or the result is the argument");
+  NH_REQUIRE(!schur->K.nrows || (z_dev != schur->z2 && z_dev != schur->t && r_dev != schur->z2 && r_dev != schur->t), "nh_schur_apply: a vector is one of the handle's scratch vectors");
+  return schur_apply(schur, r_dev, z_dev, nh_stream(stream));
+}
+
+int nh_fgmres_iterate_schur(const nh_csr *A, const unsigned char *rowmask_dev, const nh_schur *schur, double *V_dev, double *Z_dev, double *z_dev, double *t_dev,
+                            double *w_dev, double *work_dev, int restart, double stop_rr, int niter, void *stream) {
+  if (int rc = check_csr("nh_fgmres_iterate_schur", A)) return rc;
+  NH_REQUIRE(A->nrows == A->ncols, "nh_fgmres_iterate_schur: the matrix must be square (got %lld x %lld)", (long long)A->nrows, (long long)A->ncols);
+  NH_REQUIRE(restart >= 1, "nh_fgmres_iterate_schur: restart must be at least 1 (got %d)", restart);
+  NH_REQUIRE(niter >= 0, "nh_fgmres_iterate_schur: negative iteration count");
+  NH_REQUIRE(stop_rr >= 0., "nh_fgmres_iterate_schur: the bound on r . r must not be negative");
+  NH_REQUIRE(schur && schur->K.nrows == A->nrows, "nh_fgmres_iterate_schur: NULL preconditioner, or one of another size");
+  NH_REQUIRE(work_dev && (!A->nrows || (V_dev && Z_dev && z_dev && t_dev && w_dev && z_dev != t_dev)),
+             "nh_fgmres_iterate_schur: NULL vector, or the preconditioner's result is its argument");
+  NH_REQUIRE(!A->nrows || (z_dev != schur->z2 && z_dev != schur->t && t_dev != schur->z2 && t_dev != schur->t), "nh_fgmres_iterate_schur: a vector is one of the handle's scratch vectors");
+  if (!A->nrows) return NH_OK;
+  hipStream_t s = nh_stream(stream);
+  for (int it = 0; it < niter; ++it) {
+    if (int rc = schur_apply(schur, z_dev, t_dev, s)) return rc;  // (also past a stop, as the cycle of nh_fgmres_iterate: its result then goes nowhere)
     if (int rc = nh_gmres_step_from(A, rowmask_dev, t_dev, Z_dev, V_dev, z_dev, w_dev, work_dev, restart, stop_rr, s)) return rc;
   }
   return NH_OK;

@@ -1249,3 +1249,52 @@ def fgmres_iterate(values, rowptr, colidx, ncols, *, rowmask, amg, V, Z, z, t, w
     `gmres_init(None, ...)` and ended by `gmres_update(None, Z, ...)`.  A step past a stop moves nothing but still runs its cycle into `t`.'''
     _lib.call('nh_fgmres_iterate', ctypes.byref(_csr(values, rowptr, colidx, ncols, col32, lanes)), device.ptr(rowmask), amg._handle, device.ptr(V), device.ptr(Z),
               device.ptr(z), device.ptr(t), device.ptr(w), device.ptr(work), int(restart), float(stop_rr), int(niter), device.stream())
+
+
+# ---- the block preconditioner of a saddle point (nh_amg.hip) -------------------------------------------
+
+def csr_schur_diagonal(values, rowptr, colidx, ncols, vt, first, dinv, *, out=None, col32=None, lanes=0):
+    '''out[i] = A_ii - sum over the entries k of row i with first[col[k]] of values[k] vt[k] dinv[col[k]] (nh_csr_schur_diagonal).  `vt`: the values of the
+    transpose on the same pattern, `first`: a uint8 device vector, `dinv`: float64; all of the matrix's size, which the kernel takes for granted: checked here.'''
+    n = rowptr.numel() - 1
+    if n != int(ncols) or vt.numel() != values.numel() or first.numel() != n or dinv.numel() != n or str(first.dtype) != 'torch.uint8':
+        raise ValueError(f'csr_schur_diagonal: a square matrix, transposed values of its length, a uint8 mask and an inverse diagonal of {n} entries are needed')
+    if out is None:
+        out = device.empty(n, 'float64')
+    _lib.call('nh_csr_schur_diagonal', ctypes.byref(_csr(values, rowptr, colidx, ncols, col32, lanes)), device.ptr(vt), device.ptr(first), device.ptr(dinv),
+              device.ptr(out), device.stream())
+    return out
+
+
+class Schur:
+    '''The handle of a block preconditioner (nh_schur_create / nh_schur_free).  `amg`: the `Amg` handle of the first block; `K`: (values, rowptr, colidx, ncols,
+    col32, lanes); `mask1`: uint8, the first field's free dofs; `sinv`: float64, 1 / shat on the second field's free dofs and 0 elsewhere.  The handle holds
+    views: this object keeps the tensors, the hierarchy's handle and its two scratch vectors alive.'''
+
+    def __init__(self, amg, K, mask1, sinv):
+        self.n = K[1].numel() - 1
+        if amg.n != self.n or int(K[3]) != self.n or mask1.numel() != self.n or sinv.numel() != self.n or str(mask1.dtype) != 'torch.uint8' or str(sinv.dtype) != 'torch.float64':
+            raise ValueError(f'Schur: a square matrix of {self.n} rows needs a hierarchy, a uint8 mask and a float64 vector of that size')
+        self._keep = amg, K, mask1, sinv, device.empty(self.n, 'float64'), device.empty(self.n, 'float64')
+        self._handle = ctypes.c_void_p()
+        _lib.call('nh_schur_create', amg._handle, ctypes.byref(_csr(*K)), device.ptr(mask1), device.ptr(sinv), device.ptr(self._keep[4]), device.ptr(self._keep[5]),
+                  ctypes.byref(self._handle))
+
+    def __del__(self):
+        handle, self._handle = getattr(self, '_handle', None), None
+        if handle:
+            _lib.load().nh_schur_free(handle)
+
+    def apply(self, r, z=None):
+        '''z = M r: sinv r, the masked product, the cycle of the first block, the sum; enqueued (nh_schur_apply)'''
+        if z is None:
+            z = device.empty(self.n, 'float64')
+        _lib.call('nh_schur_apply', self._handle, device.ptr(r), device.ptr(z), device.stream())
+        return z
+
+
+def fgmres_iterate_schur(values, rowptr, colidx, ncols, *, rowmask, schur, V, Z, z, t, w, work, restart, stop_rr, niter, col32=None, lanes=0):
+    '''`fgmres_iterate` with the application of a `Schur` handle in place of the cycle (nh_fgmres_iterate_schur): t = M z, Z[count] = t, then the Arnoldi step
+    on A t; twelve launches, a product and a cycle each.  The matrix is that of the solve; the handle keeps the one it was built on.'''
+    _lib.call('nh_fgmres_iterate_schur', ctypes.byref(_csr(values, rowptr, colidx, ncols, col32, lanes)), device.ptr(rowmask), schur._handle, device.ptr(V),
+              device.ptr(Z), device.ptr(z), device.ptr(t), device.ptr(w), device.ptr(work), int(restart), float(stop_rr), int(niter), device.stream())

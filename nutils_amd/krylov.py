@@ -139,14 +139,15 @@ class Minres(Recurrence):
 class Fgmres(Recurrence):
     '''a start begins a cycle of up to `cycle` Arnoldi steps, which ends with x += M^-1 V y.  With an 'amg' object the method is flexible in earnest: step j keeps
     Z_j = M v_j, what the V-cycle returned, and the cycle ends with x += Z y: `cycle` more vectors on the device, 2 cycle + 1 in all.  A step enqueued past a
-    stop moves nothing but still runs its V-cycle, so a look of that variant enqueues no more steps than the cycle has left.'''
+    stop moves nothing but still runs its V-cycle, so a look of that variant enqueues no more steps than the cycle has left.  A 'schur' object (the block
+    preconditioner of a saddle point) takes the same branch with its own entry point, nh_fgmres_iterate_schur.'''
 
     name = 'fgmres'
     since = rr_start = None  # since: cycles finished since one ended on a vanished direction (0: the last one did)
     left = None  # the 'amg' variant: the steps its cycle has left
 
     def __init__(self, A, rhs, free, lhs, precon, on_device, restart):
-        cycle = _ready(precon) and precon.kind == 'amg'
+        cycle = _ready(precon) and precon.kind in ('amg', 'schur')
         super().__init__(A, rhs, free, lhs, None if cycle else precon, on_device)
         m = self.cycle = max(1, min(restart, int(free.sum())))  # (a Krylov space has no more dimensions than there are free dofs)
         k, csr, opts, dinv, x, r, (z, w) = self.kernels, self.csr, self.opts, self.dinv, self.x, self.r, self.vectors(2)
@@ -156,7 +157,11 @@ class Fgmres(Recurrence):
             (t,), (Z,), hierarchy = self.vectors(1), self.vectors(1, m * A.shape[0]), precon.hierarchy  # (the closure keeps the hierarchy alive, as Cg's does)
             self.left = m
             self.init = lambda: k.gmres_init(None, r, V, z, work, restart=m)
-            self.iterate = lambda steps, stop_rr: k.fgmres_iterate(*csr, amg=hierarchy.handle, V=V, Z=Z, z=z, t=t, w=w, work=work, restart=m, stop_rr=stop_rr, niter=steps, **opts)
+            if precon.kind == 'schur':  # the block solve of a saddle point in place of the cycle: the same vectors and rules
+                schur = precon.schur
+                self.iterate = lambda steps, stop_rr: k.fgmres_iterate_schur(*csr, schur=schur.handle, V=V, Z=Z, z=z, t=t, w=w, work=work, restart=m, stop_rr=stop_rr, niter=steps, **opts)
+            else:
+                self.iterate = lambda steps, stop_rr: k.fgmres_iterate(*csr, amg=hierarchy.handle, V=V, Z=Z, z=z, t=t, w=w, work=work, restart=m, stop_rr=stop_rr, niter=steps, **opts)
             self.update = lambda: k.gmres_update(None, Z, x, work, restart=m)
             return
         self.init = lambda: k.gmres_init(dinv, r, V, z, work, restart=m)

@@ -552,7 +552,9 @@ class HipMatrix:
         'amg' object 'fgmres' is flexible GMRES (nh_fgmres_iterate): step j keeps Z_j = M v_j, what the V-cycle returned, and the cycle ends with x += Z y, which
         is right whatever the cycle is -- not symmetric, not convergent on its own, built from other values.  That is `restart` more vectors of n doubles on the
         device, 2 restart + 1 in all; a step is ten launches and a V-cycle, and a look enqueues no more steps than the cycle has left, since a step past a stop
-        would still run its V-cycle.  Anything that is neither 'diag', 'amg', None nor such an object is an invalid preconditioner: Python callables are not
+        would still run its V-cycle.  A 'schur' object (`getprecon`: the block preconditioner of a saddle point, which has no usable 'diag' or 'amg') goes to
+        'fgmres' alone, by the same flexible iteration with the block solve in place of the cycle (nh_fgmres_iterate_schur); 'cg', 'bicgstab' and 'minres'
+        refuse it as they refuse an 'amg' object built with symmetric=False.  Anything that is neither 'diag', 'amg', None nor such an object is an invalid preconditioner: Python callables are not
         accepted, a host callback per step would undo the enqueued loop.
 
         solver='minres': MINRES of Paige and Saunders on the device for a SYMMETRIC matrix, definite or not, and ONE right-hand side, with the keywords, the row
@@ -594,7 +596,7 @@ class HipMatrix:
                 raise MatrixError('preconargs are the arguments of a preconditioner that `solve` builds; one that `getprecon` has built took them there')
             if precon.shape != self.shape:
                 raise MatrixError(f'the preconditioner was built for a {precon.shape[0]}x{precon.shape[1]} matrix, this one is {nrows}x{ncols}')
-            if precon.kind == 'amg' and solver in ('bicgstab', 'minres'):
+            if precon.kind in ('amg', 'schur') and solver in ('bicgstab', 'minres'):
                 raise MatrixError(f"HipMatrix solver {solver!r} takes a 'diag' preconditioner or None; an 'amg' preconditioner goes to 'fgmres' (any matrix) or, built with symmetric=True, to 'cg'")
             if solver == 'cg' and not precon.symmetric:
                 raise MatrixError("solver 'cg' needs a symmetric preconditioner, this one was built with symmetric=False: it goes to 'fgmres'")
@@ -763,6 +765,17 @@ class HipMatrix:
         structurally: the aggregation says so otherwise): the dense level is inverted by the general pseudo-inverse, smoother='chebyshev' is a MatrixError (its
         bound is a Lanczos estimate), everything else is the same; such an object goes to `solve(solver='fgmres')` alone.
         'diag': the inverse diagonal, for every solver that takes precon='diag', with the same bytes on the same matrix; no arguments.
+        'schur': the block preconditioner of a saddle point K = [[A, Bt], [B, C]] with C zero or small, where 'diag' finds zeros on the diagonal and 'amg' no
+        elliptic operator: ``getprecon('schur', constrain=cons, second=pmask, schur=None, first=dict(coarse=256, sweeps=1, nullspace=None, setup=None))``.
+        `second` (required): a bool mask of shape (n,) or strictly increasing indices, the dofs of the second field (the pressure); the first field is the
+        rest, and both must have free dofs.  `first`: the arguments of the 'amg' cycle on the first block, checked as above (smoother='chebyshev' is refused as
+        with symmetric=False; a `nullspace` has the shape (n, k) and is read on the first field's free dofs only); the hierarchy is built on K itself with
+        those dofs as its row mask -- no submatrix is formed, the symbolic phase goes through the cache.  `schur`: the diagonal shat of an approximate Schur
+        complement as a float vector of shape (n,), host array or device tensor, read on the second field's free dofs (for Stokes -diag(Mp) / nu); None is the
+        SIMPLE choice shat_i = K_ii - sum_j K_ij K_ji / K_jj over the first field's free dofs j, computed on the device (nh_csr_schur_diagonal) with K_ji
+        from the transpose, for which the pattern must be structurally symmetric.  A zero or non-finite shat_i is a MatrixError.  z = M r is the block
+        upper-triangular solve z2 = r / shat, z1 = cycle(r - K z2), z = z1 + z2; r is not read on held dofs and z is zero there.  The object has
+        symmetric=False whatever `symmetric` says and goes to `solve(solver='fgmres')` alone (nh_fgmres_iterate_schur).
 
         The object keeps alive what it reads: the hierarchy with its handle and level values, the value tensor it was built on, the masks.  It may be used on
         another matrix of the same shape and pattern (a matrix made by `_with_values`: the next Newton step, K + c M): that is a lagged preconditioner, which
@@ -781,14 +794,101 @@ class HipMatrix:
         elif precon == 'diag':
             if args:
                 raise MatrixError(f"invalid arguments {sorted(args)} for the 'diag' preconditioner: it takes none")
+        elif precon == 'schur':
+            second, shat, first = self._schur_args(args)
+            rest, setup = amg.split_setup(first)
+            rest, smoother = amg.split_smoother(rest)
+            if smoother is not None:
+                raise MatrixError("amg: smoother='chebyshev' takes its bound from a Lanczos estimate, which needs a symmetric matrix; with symmetric=False the smoother is 'jacobi'")
+            coarse, sweeps, nullspace = amg.check_args(rest, ncols)
         else:
-            raise MatrixError(f"invalid preconditioner {precon!r} for HipMatrix.getprecon: 'diag' or 'amg'")
+            raise MatrixError(f"invalid preconditioner {precon!r} for HipMatrix.getprecon: 'diag', 'amg' or 'schur'")
         free, _ = constraints(ncols, _host(constrain))
+        if precon == 'schur':
+            return self._schur(free, second, shat, coarse, sweeps, nullspace, setup)
         mask = None if free.all() else device.to_dev(free, 'uint8')
         if precon == 'diag':
             return amg.Preconditioner('diag', self.shape, free, True, self.triplet()[0], mask, dinv=self._dinv(mask))
         hierarchy = self._amg_hierarchy(free, mask, coarse, sweeps, nullspace, smoother, setup, symmetric=bool(symmetric))
         return amg.Preconditioner('amg', self.shape, free, symmetric, self.triplet()[0], mask, hierarchy=hierarchy)
+
+    def _schur_args(self, args):
+        '''(second, schur, first) of ``getprecon('schur', ...)``, validated on the host: `second` as a bool mask, `schur` None, a float host array or a device tensor
+        of shape (n,), `first` a dict'''
+        n = self.shape[1]
+        args = dict(args)
+        second, shat, first = args.pop('second', None), args.pop('schur', None), args.pop('first', None)
+        if args:
+            raise MatrixError(f"invalid arguments {sorted(args)} for the 'schur' preconditioner: 'second', 'schur' and 'first'")
+        if second is None:
+            raise MatrixError("schur: `second` is required: a bool mask of shape (n,) or strictly increasing indices that name the dofs of the second field (the pressure)")
+        try:
+            second = numpy.asarray(_host(second))
+        except Exception:
+            raise MatrixError(f'schur: second must be a bool mask or an integer array, got {type(second).__name__}') from None
+        if second.ndim != 1 or second.dtype != bool and second.dtype.kind not in 'iu' or second.dtype == bool and len(second) != n:
+            raise MatrixError(f'schur: second must be a bool mask of shape ({n},) or a vector of integer indices, got shape {second.shape} and dtype {second.dtype}')
+        if second.dtype != bool:
+            if second.size and (int(second.min()) < 0 or int(second.max()) >= n):
+                raise MatrixError(f'schur: second has an index outside 0 .. {n - 1}')
+            if second.size > 1 and not (second[1:] > second[:-1]).all():
+                raise MatrixError('schur: the indices of second must be strictly increasing')
+            index, second = second, numpy.zeros(n, dtype=bool)
+            second[index] = True
+        if first is not None and not isinstance(first, dict):
+            raise MatrixError(f"schur: first must be a dict of the arguments of the 'amg' cycle on the first block, got {type(first).__name__}")
+        if shat is not None:
+            tensor = _is_tensor(shat)
+            if not tensor:
+                try:
+                    shat = numpy.asarray(shat)
+                except Exception:
+                    raise MatrixError(f'schur: schur must be a float vector of shape ({n},), got {type(shat).__name__}') from None
+            if tuple(shat.shape) != (n,) or 'float' not in str(shat.dtype):
+                raise MatrixError(f'schur: schur must be a float vector of shape ({n},), got shape {tuple(shat.shape)} and dtype {shat.dtype}')
+            if not tensor:
+                shat = shat.astype(float)
+        return second, shat, first
+
+    @staticmethod
+    def _schur_bad(shat, f2):
+        '''whether shat, a host array or a device tensor, has a zero or non-finite entry where the mask f2 (of the same kind) is set'''
+        finite = shat.isfinite() if _is_tensor(shat) else numpy.isfinite(shat)
+        return bool(((shat == 0) | ~finite)[f2].any())
+
+    def _schur(self, free, second, shat, coarse, sweeps, nullspace, setup):
+        '''the 'schur' object of `getprecon`: the hierarchy of the first block on this matrix with the mask f1, the Schur diagonal (given, or the SIMPLE choice
+        by nh_csr_schur_diagonal), and the handle that applies the two'''
+        from . import amg, device, kernels
+        torch = device.torch()
+        f1, f2 = free & ~second, free & second
+        if not f1.any() or not f2.any():
+            raise MatrixError(f'schur: both fields need free dofs: the first has {int(f1.sum())}, the second {int(f2.sum())} (of {int(free.sum())} free dofs, {int(second.sum())} in `second`)')
+        message = 'schur: the diagonal of the approximate Schur complement has zero or non-finite entries on the free dofs of the second field'
+        if shat is not None and not _is_tensor(shat) and self._schur_bad(shat, f2):
+            raise MatrixError(message)
+        # -- the device from here on
+        mask = None if free.all() else device.to_dev(free, 'uint8')
+        mask1, f2_dev = device.to_dev(f1, 'uint8'), device.to_dev(f2, 'uint8') != 0
+        values, rowptr, colidx = self.triplet()
+        vt = None
+        if shat is None:
+            vt, rowptr_t, colidx_t = self.T.triplet()  # (the plan of the transpose stays on the matrix: the next one on this pattern pays one gather)
+            if not (rowptr_t.shape == rowptr.shape and colidx_t.shape == colidx.shape and torch.equal(rowptr_t, rowptr) and torch.equal(colidx_t, colidx)):
+                raise MatrixError('schur: the SIMPLE diagonal K_ii - sum_j K_ij K_ji / K_jj reads K_ji where K_ij lies, and the pattern of this matrix is not structurally '
+                                  'symmetric: pass the diagonal of an approximate Schur complement as schur=')
+        hierarchy = self._amg_hierarchy(f1, mask1, coarse, sweeps, nullspace, None, setup, symmetric=False)
+        if vt is not None:
+            shat = kernels.csr_schur_diagonal(values, rowptr, colidx, self._ncols, vt, mask1, hierarchy.data[0].dinv, col32=self._columns(), lanes=self.lanes)
+        elif _is_tensor(shat):
+            shat = shat.to(torch.float64).contiguous()
+        else:
+            shat = device.to_dev(shat, 'float64')
+        if self._schur_bad(shat, f2_dev):
+            raise MatrixError(message)
+        sinv = (1. / shat).masked_fill(~f2_dev, 0.)
+        schur = amg.Schur(hierarchy, (values, rowptr, colidx, self._ncols, self._columns(), self.lanes), mask1, sinv)
+        return amg.Preconditioner('schur', self.shape, free, False, values, mask, hierarchy=hierarchy, schur=schur)
 
     def _amg_hierarchy(self, free, mask, coarse, sweeps, nullspace=None, smoother=None, setup=None, *, symmetric=True):
         '''the hierarchy of an 'amg' preconditioner (amg.Hierarchy): the symbolic phase is taken from the cache if it was made for this mask, this `coarse`,

@@ -422,6 +422,17 @@ class System:
             out[t] = x[a:b].reshape(shape)
         return out
 
+    def trialmask(self, *names):
+        '''The bool mask over the packed vector (the rows and columns of the Jacobian) of the dofs of the named trial arguments: what
+        ``jac.getprecon('schur', second=system.trialmask('p'))`` takes, without knowing the layout.'''
+        mask = numpy.zeros(self.size, dtype=bool)
+        for name in names:
+            if name not in self.trials:
+                raise ValueError(f'{name!r} is not a trial argument of this system: {", ".join(self.trials)}')
+            i = self.trials.index(name)
+            mask[self.offsets[i]:self.offsets[i + 1]] = True
+        return mask
+
     # -- solves --
 
     def _linear_solve(self, jac, res, linargs, lenient=False, **kwargs):

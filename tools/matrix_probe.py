@@ -43,10 +43,18 @@
     object (`getprecon('amg', symmetric=False)`, with and without the symbolic phase: the second is what a reused object saves every later solve), at restart
     10 and 30 the time of a step against a Jacobi-GMRES step and one cycle of the same run, their windows alternating, and steps, wall time (the median of
     three) and true residual of the solve to rtol = 1e-8 against Jacobi-GMRES at the same restart and Jacobi-BiCGStab in the same process; and a solve of
-    the matrix one perturbation of the values further (off-diagonal entries scaled by factors within 10 % of one) with the old object against its own.
+    the matrix one perturbation of the values further (off-diagonal entries scaled by factors within 10 % of one) with the old object against its own,
+  * for the block preconditioner of a saddle point (section 'saddle', not in the default and not tied to --matrices; nh_schur_*, nh_fgmres_iterate_schur): one
+    line per size of --stokes, the lid-driven Stokes problem on n x n Taylor-Hood elements (u of degree 2, p of degree 1) from the front end through
+    solver.System: the setup of the object (`getprecon('schur')` with the SIMPLE diagonal and the component indicators as near-nullspace; first, and again on
+    the next matrix of the pattern, where the symbolic phase and the plan of the transpose are there), one application against one product, and steps, wall
+    time (the median of three) and true residual of the solve to rtol = 1e-8 by flexible GMRES(30) with the object -- built beforehand -- against BiCGStab,
+    GMRES(30) and MINRES without a preconditioner in the same process, each capped at --maxiter iterations, the same object at restart 100, and an object
+    whose Schur diagonal is minus the diagonal of the pressure mass matrix (`schur=`) at restart 30; and a solve of the matrix whose first block is
+    1.05 A + 0.03 diag(A) with the old object against its own.
 
 Usage: python tools/matrix_probe.py [--matrices poisson128,elasticity96,elasticity64,elasticity48,bilinear2048,bilinear1024,p2vector32,p2vector16] [--scale 1.0]
-[--sections spmv,cg,bicgstab,fgmres,minres,amg,smoother,algebra,columns,flexible] [--amg-setup entry,block] [--eigratios 4,10,30] [--eigsteps 5,10,20] [--out FILE]
+[--sections spmv,cg,bicgstab,fgmres,minres,amg,smoother,algebra,columns,flexible,saddle] [--stokes 16,32,64] [--amg-setup entry,block] [--eigratios 4,10,30] [--eigsteps 5,10,20] [--out FILE]
 (--scale shrinks every mesh for a quick look; --sections leaves parts out).  Not run by any test.'''
 import argparse
 import json
@@ -901,6 +909,94 @@ def probe_minres(A, free, mask, rhs_dev, res0, args):
     return out
 
 
+def probe_saddle(ne, args):
+    import torch
+    from nutils_amd import device, function, matrix, mesh
+    from nutils_amd.solver import System
+    domain, geom = mesh.unitsquare(ne, 'square')
+    u, v = (domain.field(name, btype='std', degree=2, shape=(2,)) for name in 'uv')
+    p, q = (domain.field(name, btype='std', degree=1) for name in 'pq')
+    grad = lambda w: function.grad(w, geom)
+    res = domain.integral(((grad(v) * grad(u)).sum(-1).sum(-1) - function.div(v, geom) * p - q * function.div(u, geom)) * function.J(geom), degree=4)
+    nn = 2 * ne + 1
+    ucons = numpy.full((nn, nn, 2), numpy.nan)
+    ucons[0] = ucons[-1] = ucons[:, 0] = ucons[:, -1] = 0.
+    ucons[1:-1, -1, 0] = 1.  # the lid
+    pcons = numpy.full((ne + 1) ** 2, numpy.nan)
+    pcons[0] = 0.
+    with matrix.backend('hip'):
+        system = System(res, trial='u,p', test='v,q')
+        t0 = time.perf_counter()
+        A = system.assemble_jacobian({})
+        device.synchronize()
+        assemble_ms = (time.perf_counter() - t0) * 1e3
+    start, free = system._pack({}, {'u': ucons.reshape(-1, 2), 'p': pcons})
+    cons = numpy.where(free, numpy.nan, start)
+    second = system.trialmask('p')
+    n = system.size
+    out = dict(name=f'stokes{ne}', elements=ne, nrows=n, nnz=A.nnz, velocity_dofs=int((~second).sum()), pressure_dofs=int(second.sum()), free=int(free.sum()),
+               rule_lanes=A.lanes, assemble_first_ms=assemble_ms)
+    B = numpy.zeros((n, 2))
+    B[~second] = numpy.tile(numpy.eye(2), (nn * nn, 1))
+    first = dict(nullspace=device.to_dev(B, 'float64'))
+    mask = device.to_dev(free, 'uint8')
+    start_dev = device.to_dev(start, 'float64')
+
+    def setup(K):
+        device.synchronize()
+        t0 = time.perf_counter()
+        M = K.getprecon('schur', constrain=cons, second=second, first=first)
+        device.synchronize()
+        return M, (time.perf_counter() - t0) * 1e3
+    M, first_ms = setup(A)
+    again = A._with_values(A.triplet()[0].clone())
+    _, cached_ms = setup(again)
+    levels = M.hierarchy.levels
+    out['setup'] = dict(first_ms=first_ms, cached_symbolic_ms=cached_ms, levels=[lv.nfree for lv in levels],
+                        operator_complexity=sum(lv.colidx.numel() for lv in levels) / A.nnz)
+    r = device.to_dev(numpy.random.default_rng(3).normal(size=n), 'float64')
+    y, z = torch.empty_like(r), torch.empty_like(r)
+    apply_t, product_t = windows([lambda: M.schur.apply(r, z), lambda: A.spmv(r, y=y)], args.window)
+    out['application'] = dict(apply=stats(apply_t), product=stats(product_t), products_per_application=float(numpy.median(apply_t) / numpy.median(product_t)))
+
+    def solve(K, **kwargs):
+        r0 = float(K.spmv(start_dev, alpha=-1., rowmask=mask).norm())
+        times, reached = [], True
+        for _ in range(3):
+            device.synchronize()
+            t0 = time.perf_counter()
+            try:
+                x = K.solve(None, constrain=cons, rtol=1e-8, maxiter=args.maxiter, **kwargs)
+            except matrix.ToleranceNotReached as e:
+                x, reached = e.best, False
+            device.synchronize()
+            times.append((time.perf_counter() - t0) * 1e3)
+            if not reached:  # (a solve that runs into the cap is timed once)
+                break
+        res = float(K.spmv(device.to_dev(x, 'float64'), alpha=-1., rowmask=mask).norm()) / r0
+        return dict(iterations=K.iterations, reached=reached, wall_ms=float(numpy.median(times)), true_residual=res)
+    out['schur_fgmres30'] = solve(A, solver='fgmres', precon=M, restart=30)
+    out['schur_fgmres100'] = solve(A, solver='fgmres', precon=M, restart=100)
+    # the other Schur diagonal: minus the diagonal of the pressure mass matrix (viscosity 1) instead of the SIMPLE choice
+    pbasis = domain.basis('std', degree=1)
+    shat = numpy.zeros(n)
+    shat[second] = -function.eval(function.as_matrix(domain.integral(function.outer(pbasis) * function.J(geom), degree=2))).diagonal()
+    mass = A.getprecon('schur', constrain=cons, second=second, first=first, schur=shat)
+    out['schur_mass_fgmres30'] = solve(A, solver='fgmres', precon=mass, restart=30)
+    for solver in ('bicgstab', 'fgmres', 'minres'):
+        out[('gmres30' if solver == 'fgmres' else solver) + '_none'] = solve(A, solver=solver, precon=None, **(dict(restart=30) if solver == 'fgmres' else {}))
+    # the next matrix of the pattern: the first block moved
+    values, rowptr, colidx = A.triplet()
+    rows = torch.repeat_interleave(torch.arange(n, device=rowptr.device), rowptr[1:] - rowptr[:-1])
+    velocity = device.to_dev(~second, 'uint8') != 0
+    one = torch.ones_like(values)
+    factor = torch.where(velocity[rows] & velocity[colidx], torch.where(rows == colidx, 1.08 * one, 1.05 * one), one)
+    moved = A._with_values(values * factor)
+    own, own_ms = setup(moved)
+    out['lagged'] = dict(own=solve(moved, solver='fgmres', precon=own, restart=30), own_setup_ms=own_ms, lagged=solve(moved, solver='fgmres', precon=M, restart=30))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--matrices', default='poisson128,elasticity96,bilinear2048,p2vector32')
@@ -912,6 +1008,7 @@ def main():
     ap.add_argument('--amg-setup', default='', help="section 'amg', vector matrices: the kinds of plan to build the rigid-body hierarchy with, side by side, e.g. entry,block")
     ap.add_argument('--eigratios', default='', help="section 'smoother': the eigratio values of further Chebyshev degree-2 rows, e.g. 4,10,30")
     ap.add_argument('--eigsteps', default='', help="section 'smoother': the eigsteps values of further Chebyshev degree-2 rows, e.g. 5,10,20")
+    ap.add_argument('--stokes', default='32', help="section 'saddle': the elements per side of the Taylor-Hood Stokes problems, e.g. 16,32,64")
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     args.sections = args.sections.split(',')
@@ -922,8 +1019,11 @@ def main():
     args.eigsteps = [int(v) for v in args.eigsteps.split(',') if v]
     import torch
     out = open(args.out, 'a') if args.out else None
-    for name in args.matrices.split(','):
-        line = json.dumps(probe(name, args))
+    runs = [lambda name=name: probe(name, args) for name in args.matrices.split(',') if name and set(args.sections) - {'saddle'}]
+    if 'saddle' in args.sections:
+        runs += [lambda ne=int(ne): probe_saddle(ne, args) for ne in args.stokes.split(',')]
+    for run in runs:
+        line = json.dumps(run())
         print(line, flush=True)
         if out:
             out.write(line + '\n')
