@@ -120,6 +120,12 @@ int nh_pattern_fused_info(const nh_pattern *p, int *nblocks, int *rows_per_block
  * [5] k_local_terms2 (thread-per-element passes in front of the owner-side reduction).  Read only: nothing in the library depends on the counts; a test
  * takes the difference around a call to see which family served it. */
 int nh_terms_launch_counts(int64_t counts[6]);
+/* the same for the element kernels of nh_assemble_matrix / nh_assemble_vector (the thread passes, owner blocks and write-once kernels these entries may route
+ * to are not counted): counts [0] k_matrix_mfma, [1] k_matrix_generic, [2] k_gram_sym, [3] k_vector_generic, and what the launcher chose for the LAST launch
+ * of each family: last[0..4] k_matrix_mfma ND, MT (M tiles), nt (N tiles), kt (k-steps), nas (active test slots); last[5..9] k_matrix_generic branch of the
+ * element loop (0 entries, 1 scalar symmetric, 2 Gram, 3 Gram symmetric), waves per element, use_w, qchunk (< nq: the points are taken in chunks), sym;
+ * last[10..14] k_gram_sym E (elements per workgroup), W (waves), NC, USE0, TRI; last[15] k_vector_generic qchunk.  Read only. */
+int nh_generic_launch_record(int64_t counts[4], int32_t last[16]);
 /* row tasks of NH_MATRIX_FUSED for vector-valued blocks built for this pattern so far (nh_owner.hip): row blocks (0: none yet, or the plan does not
  * apply), node rows per block, element visits of all blocks, chunks of 64 contributions */
 int nh_pattern_owner_info(const nh_pattern *p, int *nblocks, int *rows_per_block, int64_t *nvisits, int64_t *nchunks);

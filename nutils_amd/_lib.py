@@ -163,6 +163,7 @@ SIGNATURES = {
     'nh_pattern_info': (ctypes.c_int, [vp, c_i64p, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), c_i64p, ctypes.POINTER(vp)]),
     'nh_pattern_fused_info': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), c_i64p, ctypes.POINTER(ctypes.c_int)]),
     'nh_terms_launch_counts': (ctypes.c_int, [c_i64p]),
+    'nh_generic_launch_record': (ctypes.c_int, [c_i64p, ctypes.POINTER(ctypes.c_int32)]),
     'nh_pattern_owner_info': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), c_i64p, c_i64p]),
     'nh_pattern_forget_connectivity': (ctypes.c_int, [vp]),
     'nh_pattern_union_count': (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, vp, vp, vp, c_i64p, vp]),

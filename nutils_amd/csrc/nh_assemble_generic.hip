@@ -11,6 +11,7 @@
 //      atomicAdd into values[slot(e,m,c,n,d)] via the element map                       (K5)
 #include "nh_common.h"
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstddef>
 #include <vector>
@@ -20,6 +21,17 @@ namespace {
 constexpr int MAXC = 4;            // components
 constexpr int MAXS = 4;            // 1 + ndims
 constexpr int LDS_BUDGET = 60000;  // bytes of D tables per workgroup (q-chunked beyond that)
+
+// launches per kernel family of nh_assemble_matrix / nh_assemble_vector since the library was loaded, and what the launcher chose for the LAST launch of each family
+// (nh_generic_launch_record): written where a launch is issued, read by nobody here
+enum { GFAM_MFMA, GFAM_GENERIC, GFAM_GRAM_SYM, GFAM_VECTOR, NGFAM };
+enum { GREC_MFMA = 0, GREC_GENERIC = 5, GREC_GRAM_SYM = 10, GREC_VECTOR = 15, NGREC = 16 };
+std::atomic<int64_t> glaunches[NGFAM];
+std::atomic<int32_t> glast[NGREC];
+inline void record_launch(int family, int first, std::initializer_list<int> choice) {
+  ++glaunches[family];
+  for (int v : choice) glast[first++] = v;
+}
 
 struct FormK {
   int nct, ncr;
@@ -419,6 +431,16 @@ __global__ __launch_bounds__(256) void k_matrix_generic(MatK p, FormK formarg) {
       __syncthreads();
     }
   }
+}
+
+// the branch of k_matrix_generic's element loop a launch takes, from the fields the kernel branches on (for nh_generic_launch_record): 0 entries, 1 scalar symmetric,
+// 2 Gram, 3 Gram symmetric
+int generic_branch(const MatK &p, const FormK &form) {
+  const bool gram = !p.cq && form.nct * form.ncr > 1;
+  if (gram && p.sym) return 3;
+  if (gram) return 2;
+  if (form.nct * form.ncr == 1 && !p.cq && p.sym && !p.exclusive) return 1;
+  return 0;
 }
 
 #include "nh_gram_sym.inc"
@@ -1013,6 +1035,7 @@ int nh_assemble_matrix(const nh_matrix_args *a, void *stream) {
       }
 #undef LAUNCHM
       if (launched) {
+        record_launch(GFAM_MFMA, GREC_MFMA, {a->ndims, x.mt, x.nt, x.kt, x.nas});
         NH_LAUNCH_CHECK();
         return NH_OK;
       }
@@ -1050,6 +1073,7 @@ int nh_assemble_matrix(const nh_matrix_args *a, void *stream) {
     if (a->ndims == 2) LAUNCH(2);
     if (a->ndims == 3) LAUNCH(3);
 #undef LAUNCH
+    record_launch(GFAM_GENERIC, GREC_GENERIC, {generic_branch(q, form), nw, q.use_w, q.qchunk, q.sym});
     NH_LAUNCH_CHECK();
     return NH_OK;
   };
@@ -1125,7 +1149,15 @@ int nh_assemble_vector(const nh_vector_args *a, void *stream) {
   if (a->ndims == 2) LAUNCH(2);
   if (a->ndims == 3) LAUNCH(3);
 #undef LAUNCH
+  record_launch(GFAM_VECTOR, GREC_VECTOR, {p.qchunk});
   NH_LAUNCH_CHECK();
+  return NH_OK;
+}
+
+int nh_generic_launch_record(int64_t counts[4], int32_t last[16]) {
+  NH_REQUIRE(counts && last, "nh_generic_launch_record: NULL argument");
+  for (int i = 0; i < NGFAM; ++i) counts[i] = glaunches[i].load();
+  for (int i = 0; i < NGREC; ++i) last[i] = glast[i].load();
   return NH_OK;
 }
 

@@ -352,6 +352,7 @@ static int nh_gram_sym_launch(const MatK &q, const FormK &form, int ndims, bool 
 #undef LAUNCHG
 #undef LAUNCHG1
 #undef LAUNCHG2
+  record_launch(GFAM_GRAM_SYM, GREC_GRAM_SYM, {E, W, form.nct, (int)g.use0, (int)(q.sym == 3)});
   NH_LAUNCH_CHECK();
   *done = true;
   return NH_OK;

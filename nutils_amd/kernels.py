@@ -358,6 +358,24 @@ def terms_launch_counts():
     return dict(zip(TERMS_FAMILIES, counts))
 
 
+GENERIC_FAMILIES = {'k_matrix_mfma': ('ND', 'MT', 'nt', 'kt', 'nas'), 'k_matrix_generic': ('branch', 'waves', 'use_w', 'qchunk', 'sym'),
+                    'k_gram_sym': ('E', 'W', 'NC', 'USE0', 'TRI'), 'k_vector_generic': ('qchunk',)}
+GENERIC_BRANCHES = ('entries', 'scalar_symmetric', 'gram', 'gram_symmetric')
+
+
+def generic_launch_record():
+    '''({kernel family: launches since the library was loaded}, {family: the launcher's choice for its last launch}) of the element kernels of
+    nh_assemble_matrix / nh_assemble_vector (nh_generic_launch_record); the branch of k_matrix_generic by its name in GENERIC_BRANCHES.'''
+    counts, last = (ctypes.c_int64 * len(GENERIC_FAMILIES))(), (ctypes.c_int32 * 16)()
+    _lib.call('nh_generic_launch_record', counts, last)
+    choice, at = {}, 0
+    for family, names in GENERIC_FAMILIES.items():
+        choice[family] = dict(zip(names, last[at:at + len(names)]))
+        at += 5
+    choice['k_matrix_generic']['branch'] = GENERIC_BRANCHES[choice['k_matrix_generic']['branch']]
+    return dict(zip(GENERIC_FAMILIES, counts)), choice
+
+
 def _qs(qs, S):
     '''term option qs = (B [S][S], field_t, field_r): point factor U_t . B . U_r'''
     if qs is None:
